@@ -1,6 +1,6 @@
 """bench.py -- SC decode throughput on MI355X (BASELINE.json metric), 1..8 GPUs, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Workload (BASELINE.json configs[2], and per GPU of configs[4]): SC decoding of (k=512, n=1024) polar
@@ -14,8 +14,16 @@ all_reduce the block-error counters (BLER) and the timing.
 
 Reported: value = codewords decoded by all ranks / max-over-ranks wall time (Mcodewords/s);
 roofline = algorithmic HBM bytes per launch (bs*(4n+4k): fp32 LLRs in, fp32 bits out) / average
-launch time from HIP events on the decode stream, against 8.0 TB/s; cpu_baseline = the C oracle
-(same algorithm, OpenMP) on host cores, rank 0 at N=1 only, bounded to ~10 s.
+launch time from HIP events on the decode stream, against 8.0 TB/s.  A plain run does no more than
+that: set up, settle, warm up, time the K steps, print the line.  --dump-outputs DIR also writes the
+bits the last timed step decoded (DIR/decoded_bits.npy); the inputs are seeded, so two builds run
+with the same arguments can be compared bit for bit.
+
+--full adds, after the timed region, everything else the line can hold: the shader clock around the
+timed region, per-launch min / median, the VALU-issue roofline and the measured HBM traffic
+(profiles/), the Monte-Carlo iteration, the other BASELINE.json configurations (configs_1,
+configs_3, mysn_sc_exact, mysn_scl) and cpu_baseline = the C oracle (same algorithm, OpenMP) on
+host cores, rank 0 at N=1 only, bounded to ~10 s.
 """
 import argparse
 import json
@@ -32,6 +40,7 @@ import torch  # noqa: E402
 METRIC = "Mcodewords/s + info-bit Gbit/s, SC n=1024 bs=65536 @1/2/4/8 GPU; BLER match"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md, chip-level parameters (spec)
 REF_BLER_2DB = 0.9999  # reference x_run SC BLER at (512,1024), 2.0 dB
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: the most one rank writes
 
 
 def parse():
@@ -61,6 +70,14 @@ def parse():
                     help="create the process group even at world size 1 (rehearses the RCCL path on one GPU)")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the (untimed-region) lines of BASELINE.json configs[1] and configs[3]")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can hold: the clock probes, "
+                         "per-launch min / median, the VALU roofline and measured traffic, the Monte-Carlo iteration, "
+                         "the other BASELINE.json configurations and the CPU baseline (each --no-* switch still "
+                         "drops its part); without it a run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded to DIR/decoded_bits.npy (float32 [rows, k]; of a "
+                         f"batch larger than {DUMP_MAX_BYTES >> 20} MiB a fixed, seeded sample of rows, in row order)")
     a = ap.parse_args()
     if a.bs is None:
         a.bs = 65536 if a.decoder == "sc" else 8192  # BASELINE.json configs[2] / configs[3]
@@ -209,6 +226,21 @@ def sim_iteration(plan, fp, k, n, bs, ebno, dev, reps=20):
                                           "error count in one kernel, nothing but the counters in HBM "
                                           "(sim_ber's path)"}
     return res
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the decoded bits of the last timed step (what sc_decode / scl_decode hand
+    their caller), as float32 path/decoded_bits.npy.  A batch larger than DUMP_MAX_BYTES is
+    sampled: the rows a generator seeded with 0 draws (without replacement, kept in row order), so
+    the same arguments always write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    bs, k = out.shape
+    rows = max(1, DUMP_MAX_BYTES // (4 * k))
+    if bs > rows:
+        idx = np.sort(np.random.default_rng(0).choice(bs, size=rows, replace=False))
+        out = out.index_select(0, torch.from_numpy(idx).to(out.device))
+    name = "decoded_bits.npy" if world == 1 else f"decoded_bits_rank{rank}.npy"
+    np.save(os.path.join(path, name), out.cpu().numpy().astype(np.float32, copy=False))
 
 
 def _time_launches(fn, steps, warmup, settle_ms, dev):
@@ -513,10 +545,10 @@ def main():
             outs.append(torch.empty((bs, k), dtype=torch.float32, device=dev))
     bits, llr, out = bitss[0], llrs[0], outs[0]
     ws = ops.scl_workspace(plan, bs, dev) if a.decoder == "scl" else None
-    cur = [0]
+    cur, last = [0], [0]
 
     def step():
-        i = cur[0]
+        i = last[0] = cur[0]
         cur[0] = (i + 1) % R
         if a.decoder == "sc":
             ops.sc_decode(plan, llrs[i], out=outs[i])
@@ -533,7 +565,9 @@ def main():
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize(dev)
-    clk_before = clock_ghz(dev)  # the shader clock just before the timed region (after the warmup)
+    # the shader clock just before the timed region (after the warmup)
+    clk_before = clock_ghz(dev) if a.full else None
+    cur[0] = 0  # the settling loop runs for a time, not a count: the timed steps start at batch 0 in every run
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -552,8 +586,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     kern_ms = e0.elapsed_time(e1) / a.steps
-    clk_after = clock_ghz(dev)  # ... and right after its last launch
-    kstats = launch_stats(step, min(a.steps, 200), dev)
+    clk_after = clock_ghz(dev) if a.full else None  # ... and right after its last launch
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, outs[last[0]], rank, world)
+    kstats = launch_stats(step, min(a.steps, 200), dev) if a.full else None
 
     cdev = dev if backend == "nccl" else torch.device("cpu")  # RCCL reduces device tensors, gloo host ones
     nerr = sum(int(torch.any(o != b, dim=-1).sum().item()) for o, b in zip(outs, bitss))
@@ -570,10 +606,10 @@ def main():
     tag = (f"{a.decoder}{'_exact' if a.fmode == 1 else ''}{'_fast' if (a.fast_scl and L > 1) else ''}_k{k}_n{n}_bs{bs}"
            + (f"_L{L}" if L > 1 else ""))
     sim_it = None
-    if a.decoder == "sc" and a.fmode == 0 and not a.no_sim_iteration:
+    if a.full and a.decoder == "sc" and a.fmode == 0 and not a.no_sim_iteration:
         sim_it = sim_iteration(plan, fp, k, n, bs, a.ebno, dev)
     configs = None
-    if a.decoder == "sc" and a.fmode == 0 and not a.no_configs and (k, n, bs) == (512, 1024, 65536):
+    if a.full and a.decoder == "sc" and a.fmode == 0 and not a.no_configs and (k, n, bs) == (512, 1024, 65536):
         # BASELINE.json configs[1] (k=128, n=256, bs=4096, SC) and configs[3] (k=512, n=1024,
         # L=8, bs=8192, SCL) on this GPU, after the headline's timed region
         c1, f1, p1, _, _ = config_line("sc", 128, 256, 4096, 1, a.ebno, dev, rank, 2000, 200)
@@ -600,7 +636,7 @@ def main():
             cs["roofline_valu"] = rv
         configs = {"configs_1": c1, "configs_3": c3, "mysn_sc_exact": cx, "mysn_scl": cs}
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.fmode == 0:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.fmode == 0:
         cpu = cpu_baseline(llr.cpu().numpy(), fp.numpy(), k, n, a.decoder, L, a.cpu_seconds)
     if rank == 0:
         line = {
@@ -625,21 +661,26 @@ def main():
             "info_gbit_s": round(total_cw * k / wall / 1e9, 4),
             "bler": round(float(blk[0].item()) / float(blk[1].item()), 6),
             "bler_reference_at_ebno": REF_BLER_2DB if (a.decoder == "sc" and k == 512 and n == 1024 and a.ebno == 2.0) else None,
+            # of the timed region's own HIP events; --full adds the measured traffic and the per-launch min / median
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic_from_profiles(tag, plan),
-                         "kernel_ms": round(kern_ms, 5), "kernel_min_ms": kstats["min_ms"],
-                         "kernel_median_ms": kstats["median_ms"], "algorithmic_bytes_per_launch": bytes_per_launch},
-            "kernel_ms_stats": dict(kstats, mean_ms=round(kern_ms, 5),
-                                    note="mean: the timed region's HIP events over back-to-back launches; min / median: one "
-                                         "event pair per launch over that many more launches after it (each pair adds "
-                                         "~2-3 us of launch gap to its launch)"),
-            "clock_ghz": {"before": clk_before, "after": clk_after,
-                          "method": "pl_clock_probe: one wave's s_memtime cycles over s_memrealtime's 100 MHz ticks, "
-                                    "launched on the decode stream right before and right after the timed region"},
-            "cpu_baseline": cpu,
-            "dist_backend": backend,
+                         "frac": round(achieved / HBM_PEAK_GBS, 5),
+                         **({"traffic": traffic_from_profiles(tag, plan)} if a.full else {}),
+                         "kernel_ms": round(kern_ms, 5),
+                         **({"kernel_min_ms": kstats["min_ms"], "kernel_median_ms": kstats["median_ms"]} if a.full else {}),
+                         "algorithmic_bytes_per_launch": bytes_per_launch},
         }
-        rv = valu_roofline(tag, kern_ms, plan)
+        if a.full:
+            line.update({
+                "kernel_ms_stats": dict(kstats, mean_ms=round(kern_ms, 5),
+                                        note="mean: the timed region's HIP events over back-to-back launches; min / median: "
+                                             "one event pair per launch over that many more launches after it (each pair "
+                                             "adds ~2-3 us of launch gap to its launch)"),
+                "clock_ghz": {"before": clk_before, "after": clk_after,
+                              "method": "pl_clock_probe: one wave's s_memtime cycles over s_memrealtime's 100 MHz ticks, "
+                                        "launched on the decode stream right before and right after the timed region"},
+                "cpu_baseline": cpu})
+        line["dist_backend"] = backend
+        rv = valu_roofline(tag, kern_ms, plan) if a.full else None
         if a.decoder == "scl" and rv is not None:
             # the list decoder is bound by VALU issue and leaf latency (0.6 % of HBM): its roofline is
             # the VALU one, the HBM figure stays next to it

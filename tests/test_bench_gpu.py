@@ -22,7 +22,7 @@ def _run(*args):
 
 @pytest.mark.parametrize("decoder", ["sc", "scl"])
 def test_bench_json_contract(decoder):
-    d = _run("--decoder", decoder, "--steps", "5", "--warmup", "1", "--cpu-seconds", "0.5", "--settle-ms", "0")
+    d = _run("--full", "--decoder", decoder, "--steps", "5", "--warmup", "1", "--cpu-seconds", "0.5", "--settle-ms", "0")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -42,3 +42,26 @@ def test_bench_json_contract(decoder):
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["sample"]
     assert cb["best_of"] == 3 and cb["single_thread"]["cores"] == 1 and cb["single_thread"]["value"] > 0
     assert d["dtype"] == ("f32" if decoder == "sc" else "f64")
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times its steps and prints the headline line only; --dump-outputs
+    writes the bits of the last timed step (the headline batch is larger than the cap: a seeded
+    sample of its rows), the same array from run to run."""
+    import numpy as np
+    dumps = []
+    for sub in ("a", "b"):
+        d = _run("--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / sub))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert key in d, key
+        for key in ("cpu_baseline", "sim_iteration", "configs_1", "configs_3", "mysn_sc_exact", "mysn_scl",
+                    "roofline_valu", "kernel_ms_stats", "clock_ghz"):
+            assert key not in d, key
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["value"] > 0 and d["dtype"] == "f32"
+        assert abs(d["value"] - 65536 / d["ms_per_step"] / 1e3) < 1e-2 * d["value"]
+        assert [f.name for f in (tmp_path / sub).iterdir()] == ["decoded_bits.npy"]
+        dumps.append(np.load(tmp_path / sub / "decoded_bits.npy"))
+    bits = dumps[0]
+    assert bits.dtype == np.float32 and bits.shape == (16384, 512) and bits.nbytes <= 64 << 20
+    assert np.isin(bits, (0.0, 1.0)).all() and 0.3 < bits.mean() < 0.7
+    np.testing.assert_array_equal(dumps[0], dumps[1])

@@ -1,7 +1,7 @@
 # Round-6 GPU steps (run on the GPU box from the repository root):  bash tools/gpu_r06.sh <step> [tag]
 #   scl    SCL parity tests, then the same-process SCL variant A/B on the bench's AWGN input
 #   tests  the whole -m gpu suite
-#   bench  bench.py (default N=1 line)
+#   bench  bench.py --full (the whole N=1 line)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out
@@ -28,7 +28,7 @@ tests)
     tail -3 $O/${tag}_pytest_gpu.log
     ;;
 bench)
-    timeout -k 10 600 python -u bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -30 $O/${tag}_bench.err; exit 1; }
+    timeout -k 10 600 python -u bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -30 $O/${tag}_bench.err; exit 1; }
     cat $O/${tag}_bench.json
     ;;
 *)

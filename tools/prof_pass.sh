@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profile evidence of the bench kernels on the GPU box.  usage: bash tools/prof_pass.sh TAG
-#  1. the driver's bench command (python bench.py) under rocprofv3 --kernel-trace --stats: kernel
+#  1. the whole bench line (python bench.py --full) under rocprofv3 --kernel-trace --stats: kernel
 #     statistics, the headline's timed window (tools/trace_window.py) and the durations of the
 #     configs[1] / configs[3] / mysn_sc_exact / mysn_scl launches (tools/trace_configs.py);
 #  2. --pmc passes, each its own run: FETCH_SIZE and WRITE_SIZE of the SC headline kernel, of the
@@ -26,7 +26,7 @@ dec_args() {
   esac
 }
 if [ -z "$SQ_ONLY" ]; then
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $T/bench -o bench -- python3 $R/bench.py > $O/${TAG}_bench_traced.json 2> $O/${TAG}_bench_traced.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $T/bench -o bench -- python3 $R/bench.py --full > $O/${TAG}_bench_traced.json 2> $O/${TAG}_bench_traced.err
 KT=$(find $T/bench -name "*kernel_trace.csv" | head -1)
 cp $(find $T/bench -name "*kernel_stats.csv" | head -1) $O/${TAG}_bench_kernel_stats.csv
 python3 $R/tools/trace_window.py $KT $O/${TAG}_bench_traced.json > $O/${TAG}_sc_trace_window.json

@@ -2,11 +2,12 @@
 
   python tools/trace_window.py KERNEL_TRACE_CSV BENCH_JSON [--kernel pl_sc_static_f32 --marker awgn_llr_kernel]
 
-bench.py launches, in order: the clock-settling steps and the --warmup steps, a shader-clock probe
+bench.py --full launches, in order: the clock-settling steps and the --warmup steps, a shader-clock probe
 (`--marker`, clock_kernel), the --steps timed steps (all the decode kernel), a second probe, then
 per-launch timings and the other measurements.  So the timed steps are the decode launches between
-the first two marker launches (traces without the probe: the `steps` decode launches before the
-first launch of the Monte-Carlo producer, awgn_llr_kernel).  Prints their average / min / max duration,
+the first two marker launches (traces without the probe, a plain run's among them: the `steps` decode
+launches before the first launch of the Monte-Carlo producer, awgn_llr_kernel, or else the last
+`steps` of the trace).  Prints their average / min / max duration,
 the roofline fraction that average implies (algorithmic bytes from the bench line), and the
 bench line's own HIP-event figure next to it.
 """
