@@ -96,19 +96,11 @@ __device__ __forceinline__ double f_ms(double x, double y, double lmax) {  // po
 #if !PL_DEV && defined(PL_SCL_DIAG_FMS_ALL) && PL_SCL_DIAG_FMS_ALL
 #error "PL_SCL_DIAG_FMS_ALL gives wrong results: development builds (-DPL_DEV=1) only"
 #endif
-#ifndef PL_SCL_FEX_FORM
-#define PL_SCL_FEX_FORM 1  // exact f: 1 = softplus.h f_exact_pm (no cancellation), 0 = the reference's expression (ocml)
-#endif
 __device__ __forceinline__ double f_ex(double x, double y, double lmax) {  // my_sn dec.py:330-339
 #if PL_SCL_DIAG_FMS_ALL  // timing diagnostic only (wrong results): min-sum in place of the exact f
     return fmin(fmin(fabs(x), fabs(y)), lmax) * (((x < 0) != (y < 0)) ? -1.0 : 1.0);
-#elif PL_SCL_FEX_FORM == 0
-    const double xc = fmax(fmin(x, lmax), -lmax), yc = fmax(fmin(y, lmax), -lmax);
-    double o = log(1.0 + exp(xc + yc));
-    o -= log(exp(xc) + exp(yc));
-    return o;
 #else
-    return pl::f_exact_pm(x, y, lmax);  // softplus.h: the same value without the cancellation
+    return pl::f_exact_pm(x, y, lmax);  // softplus.h: the reference's expression without its cancellation
 #endif
 }
 template <int FM>
@@ -522,11 +514,11 @@ int launch_scl(const pl_plan* p, const float* llr, int64_t bs, void* out, int ou
     const bool fast = (p->flags & PL_PLAN_FAST_SCL) != 0;
     const bool exact = p->f_mode == PL_F_EXACT;
     const void* fn = nullptr;
-#define PL_SCL_PICK(O, F, P) if (out_kind == O && (exact ? 1 : 0) == F && fast == P) fn = (const void*)scl_decode_kernel<O, F, P>;
-    PL_SCL_PICK(PL_OUT_F32, 0, false) PL_SCL_PICK(PL_OUT_F32, 0, true) PL_SCL_PICK(PL_OUT_F32, 1, false)
-    PL_SCL_PICK(PL_OUT_F32, 1, true) PL_SCL_PICK(PL_OUT_U8, 0, false) PL_SCL_PICK(PL_OUT_U8, 0, true)
-    PL_SCL_PICK(PL_OUT_U8, 1, false) PL_SCL_PICK(PL_OUT_U8, 1, true)
-#undef PL_SCL_PICK
+#define PL_PICK_SCL(O, F, P) if (out_kind == O && (exact ? 1 : 0) == F && fast == P) fn = (const void*)scl_decode_kernel<O, F, P>;
+    PL_PICK_SCL(PL_OUT_F32, 0, false) PL_PICK_SCL(PL_OUT_F32, 0, true) PL_PICK_SCL(PL_OUT_F32, 1, false)
+    PL_PICK_SCL(PL_OUT_F32, 1, true) PL_PICK_SCL(PL_OUT_U8, 0, false) PL_PICK_SCL(PL_OUT_U8, 0, true)
+    PL_PICK_SCL(PL_OUT_U8, 1, false) PL_PICK_SCL(PL_OUT_U8, 1, true)
+#undef PL_PICK_SCL
     if (y.bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, y.bytes);
         if (e != hipSuccess) return check_hip(e, "SCL decode: LDS attribute");

@@ -45,74 +45,54 @@
 
 namespace {
 
-// Tuning macros (A/B variants: tools/scl_variants.py)
-#ifndef PL_SCL_R
-#define PL_SCL_R 4  // stage of the lane-local subtree (4 or 5; A/B on MI355X: 4 is 19 % faster)
-#endif
-#ifndef PL_SCL_LOADGRP
-#define PL_SCL_LOADGRP 0  // > 0: stage-R input read in groups of this many pairs (caps VGPRs)
-#endif
-#ifndef PL_SCL_UNROLL
-#define PL_SCL_UNROLL 1  // 1: the 2^R leaves of a lane-local subtree fully unrolled (A/B: 2.08 vs 2.27 ms; round 6,
-                        // constant leaf indices via unroll_leaves: 0.793 -> 0.744 ms, profiles/r06d_scl_unroll_ab.txt)
-#endif
+// Compile-time macros.  The unit selectors PL_SCL_TREE_L / PL_SCL_TREE_DISPATCH (end of the file; the
+// variant libraries of tools/scl_variants.py add PL_SCL_VARIANT_ONLY_L8) and, in development
+// builds (-DPL_DEV=1) only, the phase timing PL_SCL_PROF and the PL_SCL_DIAG_* ablations below.
+// Every tuning decision is folded into the code with the measurement that settled it; an A/B of a
+// new alternative adds its switch for the experiment (tools/scl_variants.py passes any -D) and
+// removes it when the decision is made.
+//
+// Timing ablations (a phase left out or made cheap; WRONG results unless noted):
 #ifndef PL_SCL_DIAG_NO_UPPER
-#define PL_SCL_DIAG_NO_UPPER 0
+#define PL_SCL_DIAG_NO_UPPER 0  // no upper-tree node passes (stored or virtual)
 #endif
 #ifndef PL_SCL_DIAG_NO_UPPER_PRUNE
-#define PL_SCL_DIAG_NO_UPPER_PRUNE 0  // timing diagnostic: fast-SCL only inside the lane subtrees (wrong)
+#define PL_SCL_DIAG_NO_UPPER_PRUNE 0  // fast-SCL pruning only inside the lane subtrees
 #endif
 #ifndef PL_SCL_DIAG_SKIP_V
-#define PL_SCL_DIAG_SKIP_V 0
+#define PL_SCL_DIAG_SKIP_V 0  // no virtual node passes
 #endif
 #ifndef PL_SCL_DIAG_SKIP_ST
-#define PL_SCL_DIAG_SKIP_ST 0
-#endif
-#ifndef PL_SCL_FROZEN_PAIR
-#define PL_SCL_FROZEN_PAIR 1  // 1: a frozen sibling leaf pair takes one exp/log per lane (shadow lanes the right leaf)
-#endif
-#ifndef PL_SCL_RANK_MASK
-#define PL_SCL_RANK_MASK 1  // 1: 16-lane rank with a static tie mask and carry-in adds (no index DPP)
-#endif
-#ifndef PL_SCL_RANK_SUBB
-#define PL_SCL_RANK_SUBB 1  // 1: 16-lane rank as 64-bit borrow chains with DPP sources (rank16_subb)
-#endif
-#ifndef PL_SCL_FG_BITS
-#define PL_SCL_FG_BITS 1  // 1: min-sum f and g sign handling on the high words (f_ms, g_op)
-#endif
-#ifndef PL_SCL_ST_UNROLL
-#define PL_SCL_ST_UNROLL 1  // 1: min-sum stored-stage node passes of 2^R / 2^(R+1) outputs unrolled, loads first
-                           // (A/B r02zk: 1.081 -> 1.050 ms)
-#endif
-#ifndef PL_SCL_ST_CH
-#define PL_SCL_ST_CH 8  // elements per lane loaded ahead in those passes
+#define PL_SCL_DIAG_SKIP_ST 0  // no stored-stage node passes
 #endif
 #ifndef PL_SCL_DIAG_NO_REPOINT
-#define PL_SCL_DIAG_NO_REPOINT 0  // timing diagnostic (wrong results)
+#define PL_SCL_DIAG_NO_REPOINT 0  // no re-pointing of the upper-tree state after a subtree
 #endif
 #ifndef PL_SCL_DIAG_NO_PULL
-#define PL_SCL_DIAG_NO_PULL 0  // timing diagnostic (wrong results)
+#define PL_SCL_DIAG_NO_PULL 0  // forks move no live stage buffers (and L = 8 min-sum selects by select_2l)
 #endif
 #ifndef PL_SCL_DIAG_NO_COMBINE
-#define PL_SCL_DIAG_NO_COMBINE 0  // timing diagnostic (wrong results)
+#define PL_SCL_DIAG_NO_COMBINE 0  // no partial-sum combines above stage R
 #endif
 #ifndef PL_SCL_DIAG_VC_NOSTORE
-#define PL_SCL_DIAG_VC_NOSTORE 0  // timing diagnostic (wrong results): no virtual-node cache stores (min-sum)
+#define PL_SCL_DIAG_VC_NOSTORE 0  // no virtual-node cache stores (min-sum)
 #endif
-// Diagnostic macros (timing ablations with WRONG results) exist only in development builds.
+#ifndef PL_SCL_DIAG_NO_RANK
+#define PL_SCL_DIAG_NO_RANK 0  // candidates keep their group lane as rank (no ranking, no speculative push)
+#endif
+#ifndef PL_SCL_DIAG_CHEAP_PEN
+#define PL_SCL_DIAG_CHEAP_PEN 0  // penalty max(-l, 0) in place of the softplus
+#endif
+#ifndef PL_SCL_DIAG_FMS_ALL
+#define PL_SCL_DIAG_FMS_ALL 0  // min-sum f in place of the exact f
+#endif
+#ifndef PL_SCL_DIAG_SPEC_FB
+#define PL_SCL_DIAG_SPEC_FB 0  // speculative push: 1 = always re-rank the pushed candidates (same results), 2 = never
+#endif
 #if !PL_DEV && (PL_SCL_DIAG_NO_UPPER || PL_SCL_DIAG_NO_UPPER_PRUNE || PL_SCL_DIAG_SKIP_V || PL_SCL_DIAG_SKIP_ST || \
-                PL_SCL_DIAG_NO_REPOINT || PL_SCL_DIAG_NO_COMBINE || PL_SCL_DIAG_NO_RANK || PL_SCL_DIAG_CHEAP_PEN || \
-                PL_SCL_DIAG_NO_PULL || PL_SCL_DIAG_FMS_ALL || PL_SCL_DIAG_VC_NOSTORE)
+                PL_SCL_DIAG_NO_REPOINT || PL_SCL_DIAG_NO_PULL || PL_SCL_DIAG_NO_COMBINE || PL_SCL_DIAG_VC_NOSTORE || \
+                PL_SCL_DIAG_NO_RANK || PL_SCL_DIAG_CHEAP_PEN || PL_SCL_DIAG_FMS_ALL || PL_SCL_DIAG_SPEC_FB)
 #error "PL_SCL_DIAG_* macros give wrong results: development builds (-DPL_DEV=1) only"
-#endif
-#ifndef PL_SCL_REPOINT_VEC
-#define PL_SCL_REPOINT_VEC 1  // 1: re-pointing in 16-byte rows, two lanes per (codeword, path) pair (n >= 128)
-#endif
-#ifndef PL_SCL_FEX_HOIST
-#define PL_SCL_FEX_HOIST 1  // 1: exact-f virtual passes evaluate the path-independent f levels once (vvisit_ex)
-#endif
-#ifndef PL_SCL_WPE
-#define PL_SCL_WPE 2  // > 0: amdgpu_waves_per_eu minimum (2: <= 256 VGPRs, A/B on MI355X: 2.30 vs 3.62 ms at V=4)
 #endif
 
 // Phase timing (development builds, tools/scl_prof.py): per wave, s_memtime cycles spent in each
@@ -121,7 +101,8 @@ namespace {
 // passes, 2 lane subtrees, 3 re-pointing and partial-sum stores, 4 combines, 5 pruned nodes and
 // right (g) virtual passes, 6 set-up (incl. exact-f caches), 7 the final butterfly / CRC / sort /
 // output; 8..11 split the lane subtrees (min-sum, no fast-SCL): leaf f/g, penalties, ranks,
-// selection moves (2 keeps the rest).
+// selection moves (2 keeps the rest; the speculative push of L = 8 overlaps its key rank with
+// the moves, so both land in 11 and 10 stays empty).
 #ifndef PL_SCL_PROF
 #define PL_SCL_PROF 0
 #endif
@@ -172,8 +153,8 @@ __shared__ unsigned long long vex_prof[3];
 #define PROF_ARG
 #endif
 
-constexpr int R = PL_SCL_R;  // stage of the lane-local subtree
-constexpr int T = 1 << R;    // leaves per lane-local subtree (<= one partial-sum word)
+constexpr int R = 4;       // stage of the lane-local subtree (A/B on MI355X against 5: 4 is 19 % faster)
+constexpr int T = 1 << R;  // leaves per lane-local subtree (<= one partial-sum word)
 constexpr int SPS = 16;      // bytes per path of the stage-owner table (S + 1 <= 16), one 16-byte row
 
 __host__ __device__ constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x >> 1); }
@@ -223,7 +204,7 @@ __host__ __device__ inline int combo_size(int n, int V) { return V >= 2 ? 2 * n 
 __host__ __device__ inline int combo_off(int n, int V, int ns) { return chain_size(n, V) + 2 * n - 4 * (n >> (ns + 1)); }
 __host__ __device__ inline int cache_size(int n, int V) { return chain_size(n, V) + combo_size(n, V); }
 
-#if PL_SCL_FG_BITS
+// Min-sum f and g handle signs on the high words (f_ms, g_op).
 // v_min_f64 without the input canonicalisation fmin() adds (a v_max_f64 per operand that is not
 // known canonical); the decoder never sees NaNs (unsupported inputs)
 __device__ __forceinline__ double min_abs_nc(double a, double b) {
@@ -236,10 +217,8 @@ __device__ __forceinline__ double min_nc(double a, double b) {
     asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
-#endif
 
 __device__ __forceinline__ double f_ms(double x, double y, double lmax) {  // polar_scl.py:93-106
-#if PL_SCL_FG_BITS
     // m >= +0, so sign(x) sign(y) m is m with the sign bit x31 ^ y31 (two 32-bit ops on the high
     // words instead of a 64-bit sign test, a negation and two selects)
     const double m = min_nc(min_abs_nc(x, y), lmax);
@@ -248,30 +227,17 @@ __device__ __forceinline__ double f_ms(double x, double y, double lmax) {  // po
     const uint32_t sy = (uint32_t)((unsigned long long)__double_as_longlong(y) >> 32);
     const uint32_t hi = (uint32_t)(mb >> 32) | ((sx ^ sy) & 0x80000000u);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (mb & 0xffffffffull)));
-#else
-    const double m = fmin(fmin(fabs(x), fabs(y)), lmax);
-    const bool neg = (__double_as_longlong(x) ^ __double_as_longlong(y)) < 0;
-    return neg ? -m : m;
-#endif
 }
-#ifndef PL_SCL_FEX_FORM
-#define PL_SCL_FEX_FORM 1  // exact f: 1 = softplus.h f_exact_pm (no cancellation), 0 = the reference's expression (ocml)
-#endif
 __device__ __forceinline__ double f_ex(double x, double y, double lmax) {  // my_sn dec.py:330-339
 #if PL_SCL_DIAG_FMS_ALL  // timing diagnostic only (wrong results): min-sum in place of the exact f
     return fmin(fmin(fabs(x), fabs(y)), lmax) * (((x < 0) != (y < 0)) ? -1.0 : 1.0);
-#elif PL_SCL_FEX_FORM == 0
-    const double xc = fmax(fmin(x, lmax), -lmax), yc = fmax(fmin(y, lmax), -lmax);
-    double o = log(1.0 + exp(xc + yc));
-    o -= log(exp(xc) + exp(yc));
-    return o;
 #else
-    return pl::f_exact_pm(x, y, lmax);  // softplus.h: the same value without the cancellation
+    return pl::f_exact_pm(x, y, lmax);  // softplus.h: the reference's expression without its cancellation
 #endif
 }
 // two exact f evaluations interleaved (independent chains overlap within the wave)
 __device__ __forceinline__ void f_ex2(double x0, double y0, double x1, double y1, double lmax, double& r0, double& r1) {
-#if PL_SCL_DIAG_FMS_ALL || PL_SCL_FEX_FORM == 0
+#if PL_SCL_DIAG_FMS_ALL
     r0 = f_ex(x0, y0, lmax);
     r1 = f_ex(x1, y1, lmax);
 #else
@@ -288,14 +254,10 @@ __device__ __forceinline__ double f_op(double x, double y, double lmax) {
     else return f_ex(x, y, lmax);
 }
 __device__ __forceinline__ double g_op(double x, double y, uint32_t bit) {  // :107-108
-#if PL_SCL_FG_BITS
     // (1 - 2u) x + y: the bit goes straight into x's sign (a shift and a xor, which the compiler
     // folds with the bit extraction, instead of a compare and a select)
     const unsigned long long xb = (unsigned long long)__double_as_longlong(x);
     return __longlong_as_double((long long)(xb ^ ((unsigned long long)(bit << 31) << 32))) + y;
-#else
-    return (bit ? -x : x) + y;
-#endif
 }
 __device__ __forceinline__ uint32_t getbit(const uint32_t* w, int pos) { return (w[pos >> 5] >> (pos & 31)) & 1u; }
 
@@ -328,27 +290,17 @@ __device__ __forceinline__ double half_xchg(double v, int lane) {
     else return bperm_d(v, lane ^ L);
 }
 
-// Candidate (metric) of group lane (gl + r) mod GW, r = 1..GW-1, accumulated into the rank of
-// this lane's candidate in the stable (metric, index) order.
-// acc + (bit `lane` of m): one v_addc with the lane mask as carry-in
-__device__ __forceinline__ int add_lane_bit(int acc, uint64_t m) {
-    int r;
-    uint64_t co;
-    asm("v_addc_co_u32_e64 %0, %1, 0, %2, %3" : "=v"(r), "=s"(co) : "v"(acc), "s"(m));
-    return r;
-}
-
-#if PL_SCL_RANK_SUBB
 // Rank of this lane's candidate in its 16-lane group (the DPP row), all 15 rotations in one
-// block.  Metrics are non-negative doubles (pm starts at 0 or llr_max > 0 and only ever adds
+// block: the full stable rank that re-ranks a misordered row of the speculative push (select_2l,
+// subtree).  Metrics are non-negative doubles (pm starts at 0 or llr_max > 0 and only ever adds
 // softplus values >= +0; never -0 or NaN), so their bit patterns order like the values, and the
 // stable (metric, index) comparison "v < cv, or v == cv with the lower index" is the 64-bit
-// unsigned v < cv + tie, tie = 1 exactly when the rotated source has the lower index (the same
-// static row mask as the ballot form above: group lanes >= r under row_ror:r).  Per rotation:
-// the tie mask into VCC as the borrow-in, v_subb on the low and high words with the rotated
-// candidate as the DPP source -- the final borrow is the comparison -- and one carry add into
-// the rank.  3 VALU (2 of them DPP) + 2 SALU, against 2 DPP moves + 2 fp64 compares + 1 add +
-// 3 SALU.
+// unsigned v < cv + tie, tie = 1 exactly when the rotated source has the lower index: under
+// row_ror:r group lane gl receives group lane (gl - r) mod 16, the lower index exactly when
+// gl >= r -- a constant row mask per rotation.  Per rotation: the tie mask into VCC as the
+// borrow-in, v_subb on the low and high words with the rotated candidate as the DPP source -- the
+// final borrow is the comparison -- and one carry add into the rank.  3 VALU (2 of them DPP) +
+// 2 SALU, against 2 DPP moves + 2 fp64 compares + 1 add + 3 SALU for a compare per rotation.
 #define PL_RANK_ROT(r, m)                                                                   \
     "s_mov_b32 vcc_lo, " #m "\n\t"                                                          \
     "s_mov_b32 vcc_hi, " #m "\n\t"                                                          \
@@ -373,91 +325,22 @@ __device__ __forceinline__ int rank16_subb(double cv) {
     return rk;
 }
 #undef PL_RANK_ROT
-#ifndef PL_SCL_RANK_SPLIT
-#define PL_SCL_RANK_SPLIT 1  // 1: two independent borrow chains (VCC / SGPR pairs) instead of one (A/B r03u: 0.985 vs 0.991 ms)
-#endif
-// The same 15-rotation rank as two independent accumulations, interleaved: rotations 1..8 on the
-// VCC borrow chain of rank16_subb, rotations 9..15 as VOP3 borrow chains through SGPR pairs on
-// DPP-moved copies (5 VALU + 1 SALU each instead of 3 + 2): ~40 dependent steps instead of 75.
-#define PL_RANK_ROT_A(r, m)                                                                   \
-    "s_mov_b32 vcc_lo, " #m "\n\t"                                                          \
-    "s_mov_b32 vcc_hi, " #m "\n\t"                                                          \
-    "v_subb_co_u32_dpp %2, vcc, %7, %7, vcc row_ror:" #r " row_mask:0xf bank_mask:0xf\n\t" \
-    "v_subb_co_u32_dpp %2, vcc, %8, %8, vcc row_ror:" #r " row_mask:0xf bank_mask:0xf\n\t" \
-    "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n\t"
-#define PL_RANK_ROT_B(r, m)                                                 \
-    "v_mov_b32_dpp %3, %7 row_ror:" #r " row_mask:0xf bank_mask:0xf\n\t" \
-    "v_mov_b32_dpp %4, %8 row_ror:" #r " row_mask:0xf bank_mask:0xf\n\t" \
-    "v_subb_co_u32_e64 %3, %5, %3, %7, " #m "\n\t"                       \
-    "v_subb_co_u32_e64 %4, %6, %4, %8, %5\n\t"                           \
-    "v_addc_co_u32_e64 %1, %5, 0, %1, %6\n\t"
-__device__ __forceinline__ int rank16_split(double cv) {
-    const long long b = __double_as_longlong(cv);
-    const int lo = (int)(b & 0xffffffffLL), hi = (int)(b >> 32);
-    int ra, rb, ta, tl, th;
-    uint64_t s1, s2;
-    // static tie masks of rotations 9..15 (group lanes >= r under row_ror:r, every row)
-    constexpr uint64_t m9 = 0xfe00fe00fe00fe00ull, m10 = 0xfc00fc00fc00fc00ull, m11 = 0xf800f800f800f800ull,
-                       m12 = 0xf000f000f000f000ull, m13 = 0xe000e000e000e000ull, m14 = 0xc000c000c000c000ull,
-                       m15 = 0x8000800080008000ull;
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mov_b32 %0, 0\n\t"
-        "v_mov_b32 %1, 0\n\t"
-        PL_RANK_ROT_A(1, 0xfffefffe) PL_RANK_ROT_B(9, %9)
-        PL_RANK_ROT_A(2, 0xfffcfffc) PL_RANK_ROT_B(10, %10)
-        PL_RANK_ROT_A(3, 0xfff8fff8) PL_RANK_ROT_B(11, %11)
-        PL_RANK_ROT_A(4, 0xfff0fff0) PL_RANK_ROT_B(12, %12)
-        PL_RANK_ROT_A(5, 0xffe0ffe0) PL_RANK_ROT_B(13, %13)
-        PL_RANK_ROT_A(6, 0xffc0ffc0) PL_RANK_ROT_B(14, %14)
-        PL_RANK_ROT_A(7, 0xff80ff80) PL_RANK_ROT_B(15, %15)
-        PL_RANK_ROT_A(8, 0xff00ff00)
-        "v_add_u32 %0, %0, %1\n\t"
-        : "=&v"(ra), "=&v"(rb), "=&v"(ta), "=&v"(tl), "=&v"(th), "=&s"(s1), "=&s"(s2)
-        : "v"(lo), "v"(hi), "s"(m9), "s"(m10), "s"(m11), "s"(m12), "s"(m13), "s"(m14), "s"(m15)
-        : "vcc");
-    return ra;
-}
-#undef PL_RANK_ROT_A
-#undef PL_RANK_ROT_B
-#endif
 
+// Candidate (metric) of group lane (gl + r) mod GW, r = 1..GW-1, accumulated into the rank of
+// this lane's candidate in the stable (metric, index) order (2L = 4, 8, 32; 2L = 16 ranks by key
+// in select_2l, 2L = 64 by readlane in rank_2l).
 template <int GW, int r>
 __device__ __forceinline__ void rank_rot(double cv, int gl, int lane, int& rk) {
-#if PL_SCL_RANK_SUBB
-    if constexpr (GW == 16 && r == 1) {
-        rk = rank16_subb(cv);
-        return;
-    }
-#endif
-#if PL_SCL_RANK_MASK
-    if constexpr (GW == 16 && r < GW) {
-        // row_ror:r -- group lane gl receives group lane (gl - r) mod 16, whose candidate index
-        // is the lower one exactly when gl >= r: that tie mask is a constant per rotation
-        const double v = dpp_d<0x120 + r>(cv);
-        constexpr uint64_t tie = (uint64_t)((0xFFFFu << r) & 0xFFFFu) * 0x0001000100010001ull;
-        const uint64_t lt = __builtin_amdgcn_ballot_w64(v < cv);
-        const uint64_t eq = __builtin_amdgcn_ballot_w64(v == cv);
-        rk = add_lane_bit(rk, lt | (eq & tie));
-        rank_rot<GW, r + 1>(cv, gl, lane, rk);
-        return;
-    }
-#endif
+    static_assert(GW != 16, "2L = 16 is ranked by rank16_key / rank16_subb");
     if constexpr (r < GW) {
         double v;
-        if constexpr (GW == 16) {
-            v = dpp_d<0x120 + r>(cv);  // row_ror:r -- the 16-lane DPP row is the group
-        } else if constexpr (GW == 4) {
+        if constexpr (GW == 4) {
             constexpr int q = ((0 + r) & 3) | (((1 + r) & 3) << 2) | (((2 + r) & 3) << 4) | (((3 + r) & 3) << 6);
             v = dpp_d<q>(cv);  // quad_perm rotation
         } else {
             v = bperm_d(cv, (lane & ~(GW - 1)) | ((gl + r) & (GW - 1)));
         }
-        // source group lane of the rotation (DPP row_ror / quad_perm / bpermute), moved like
-        // the value so the direction convention cannot matter
-        int ci;
-        if constexpr (GW == 16) ci = __builtin_amdgcn_mov_dpp(gl, 0x120 + r, 0xF, 0xF, true);
-        else ci = (gl + r) & (GW - 1);
+        const int ci = (gl + r) & (GW - 1);  // source group lane of the rotation
         rk += (v < cv || (v == cv && ci < gl)) ? 1 : 0;
         rank_rot<GW, r + 1>(cv, gl, lane, rk);
     }
@@ -620,17 +503,12 @@ __device__ __forceinline__ void vlev_shared(double* vx, double* vy, double lmax)
 // handles item (c, j) in one pass handles it in every pass.  Half the passes then cost one load
 // and one g per path instead of 31 f/g.  Min-sum also keeps the stage-7 values (after the
 // level that produces them, in the left pass of a stage-7 node's left child): the left pass of
-// its right child then starts from them (one g per side and the f) instead of the channel.
-#ifndef PL_SCL_VCACHE
-#define PL_SCL_VCACHE 1
-#endif
-#ifndef PL_SCL_C7
-#define PL_SCL_C7 1  // 1: min-sum caches the stage-7 values too (A/B r04i, one path per step: 0.942 vs
-                     // 0.929 ms; with the batched loads, r04q: 0.868 vs 0.893 ms)
-#endif
+// its right child then starts from them (one g per side and the f) instead of the channel (A/B
+// r04i, one path per step: 0.942 vs 0.929 ms without; with the batched loads, r04q: 0.868 vs
+// 0.893 ms).
 // The stage-7 cache at L <= 8 only: the wider lists' kernels spill with it (L = 16: 38 VGPRs).
 template <int L, int FM>
-constexpr bool c7_on() { return PL_SCL_C7 && FM == 0 && L <= 8; }
+constexpr bool c7_on() { return FM == 0 && L <= 8; }
 constexpr int kVcEntries = 32;  // (item, path) entries per lane: IT * L <= 32 (node_fg checks it)
 template <int FM>
 struct VCache {
@@ -639,17 +517,15 @@ struct VCache {
 template <>
 struct VCache<0> {  // min-sum
     double2 v[kVcEntries];
-#if PL_SCL_C7
     double4 v7[kVcEntries];  // the stage-7 elements (j, j + 64 | j + 32, j + 96) of the same path
     int p7;          // start of the stage-7 node v7 belongs to (fast-SCL may prune the left pass
                      // that writes it: the right child's pass then recomputes); same in every lane
-#endif
 };
 
 template <int L, int V, int NS, int FM>
 __device__ __forceinline__ void vnode64(const St& t, const Cw& w, const float* cx, const float* cy, const int* wb,
-                                        int j, uint32_t gmask, bool is_g, int pos, int ls, VCache<FM>* vc = nullptr,
-                                        int it = 0, bool w7 = false) {
+                                        int j, uint32_t gmask, bool is_g, int pos, int ls, VCache<FM>* vc, int it,
+                                        bool w7) {
     constexpr int H = 1 << (V - 1);       // values per side after the channel level
     constexpr int NSS = (NS == V && c7_on<L, FM>()) ? V - 1 : NS;  // shared levels (C7: before the stage-7 boundary)
     constexpr int K = NSS > 0 ? (2 * H) >> NSS : 2 * H;  // per side after those shared levels
@@ -692,9 +568,7 @@ __device__ __forceinline__ void vnode64(const St& t, const Cw& w, const float* c
             vlev_range<V - NSS - 1, 1, FM>(vx, vy, bp, wb, j, gmask, t.lmax);
         }
         // the stage-7 values (levels above done): cached for the right child's left pass
-#if PL_SCL_C7
         if (w7 && !PL_SCL_DIAG_VC_NOSTORE) vc->v7[it * L + p] = make_double4(vx[0], vx[1], vy[0], vy[1]);
-#endif
         if constexpr (NSS == V) {  // every level shared: nothing per path
         } else if constexpr (NS == V) {  // C7: level 0 is the last shared f (same value for every path)
             vlev_f<0, FM>(vx, vy, t.lmax);
@@ -711,13 +585,9 @@ __device__ __forceinline__ void vnode64(const St& t, const Cw& w, const float* c
 // entry and partial-sum word of the pass is loaded before the first g, so the private-memory loads
 // (L2 latency) overlap instead of being paid once per path (r04n phase timing: 12.7k cycles per pass
 // with one path per step).
-#ifndef PL_SCL_VC_BATCH
-#define PL_SCL_VC_BATCH 1
-#endif
 template <int L, int FM>
 __device__ __forceinline__ void vnode64_cached(const St& t, const Cw& w, int j, int pos, int ls, const VCache<FM>& vc,
                                                int it) {
-#if PL_SCL_VC_BATCH
     constexpr int B = L < 8 ? L : 8;  // paths per batch (registers: 6 per path)
 #pragma unroll
     for (int p0 = 0; p0 < L; p0 += B) {
@@ -735,23 +605,13 @@ __device__ __forceinline__ void vnode64_cached(const St& t, const Cw& w, int j, 
         for (int q = 0; q < B; ++q)
             w.A[(p0 + q) * t.per + (1 << ls) - (1 << R) + j] = g_op(xy[q].x, xy[q].y, (wd[q] >> ((pos + j) & 31)) & 1u);
     }
-#else
-#pragma unroll 1
-    for (int p = 0; p < L; ++p) {
-        const int o = w.sptr[p * SPS + ls + 1];
-        const double2 xy = vc.v[it * L + o];
-        w.A[p * t.per + (1 << ls) - (1 << R) + j] = g_op(xy.x, xy.y, getbit(w.beta + p * t.W, pos + j));
-    }
-#endif
 }
 
 // The left pass of a stage-7 node's right child (level 0 a g) from the stage-7 cache: per path,
 // the owner's four values, one g per side, the f, and the stage-6 entry for the right pass.
-#if PL_SCL_C7
 template <int L>
 __device__ __forceinline__ void vnode64_c7(const St& t, const Cw& w, int j, int pos, int ls, VCache<0>& vc, int it) {
     const int p7 = pos & ~127;  // start of the stage-7 node: the left child's partial sums
-#if PL_SCL_VC_BATCH
     constexpr int B = L < 8 ? L : 8;  // paths per batch (registers: 10 per path)
 #pragma unroll
     for (int p0 = 0; p0 < L; p0 += B) {
@@ -772,18 +632,7 @@ __device__ __forceinline__ void vnode64_c7(const St& t, const Cw& w, int j, int 
             w.A[(p0 + q) * t.per + (1 << ls) - (1 << R) + j] = f_ms(x, y, t.lmax);
         }
     }
-#else
-#pragma unroll 1
-    for (int p = 0; p < L; ++p) {
-        const uint32_t* bp = w.beta + p * t.W;
-        const double4 c = vc.v7[it * L + w.sptr[p * SPS + ls + 2]];
-        const double x = g_op(c.x, c.y, getbit(bp, p7 + j)), y = g_op(c.z, c.w, getbit(bp, p7 + 32 + j));
-        if (!PL_SCL_DIAG_VC_NOSTORE) vc.v[it * L + p] = make_double2(x, y);
-        w.A[p * t.per + (1 << ls) - (1 << R) + j] = f_ms(x, y, t.lmax);
-    }
-#endif
 }
-#endif
 
 // One pass of a virtual node of 64 over the wave's (codeword, element) pairs; NS leading f
 // levels (a per-pass constant, so each NS is its own loop).
@@ -792,20 +641,13 @@ __device__ void vvisit64(const St& t, int pos, bool is_g, int lane, const int* w
     constexpr int NC = 1 << V, ls = 5, h = 32, hs = 64;
     static_assert((CPW * h + 63) / 64 * L <= kVcEntries, "VCache: items per lane x paths");
     if (vc != nullptr && is_g) {
-#if PL_SCL_VC_BATCH
 #pragma unroll
         for (int it = 0; it < (CPW * h + 63) / 64; ++it) {  // CPW * h = 32 at L = 32: half the lanes
             const int idx = lane + 64 * it;
             if (CPW * h % 64 == 0 || idx < CPW * h) vnode64_cached<L, FM>(t, t.cw(idx >> ls), idx & (h - 1), pos, ls, *vc, it);
         }
-#else
-#pragma unroll 1
-        for (int idx = lane, it = 0; idx < CPW * h; idx += 64, ++it)
-            vnode64_cached<L, FM>(t, t.cw(idx >> ls), idx & (h - 1), pos, ls, *vc, it);
-#endif
         return;
     }
-#if PL_SCL_C7
     if (c7_on<L, FM>() && vc != nullptr && (pos & 127) == 64 && vc->p7 == pos - 64) {  // right child of its stage-7 node
 #pragma unroll
         for (int it = 0; it < (CPW * h + 63) / 64; ++it) {
@@ -816,48 +658,8 @@ __device__ void vvisit64(const St& t, int pos, bool is_g, int lane, const int* w
     }
     const bool w7 = c7_on<L, FM>() && vc != nullptr && (pos & 127) == 0;  // a new stage-7 node
     if (w7) vc->p7 = pos;
-#else
-    const bool w7 = false;
-#endif
     // channel rows addressed from the wave's first row (uniform base, 32-bit lane offsets)
     const float* ch0 = t.llr + t.b0 * t.n;
-#if PL_SCL_VPF
-    // software-pipelined by one element: the next element's 2 x 2^V channel values (L2) are in
-    // flight while this one's paths are evaluated (CPW * h is a multiple of 64: uniform trip count)
-    auto co_of = [&](int idx) {
-        const int c = idx >> ls, j = idx & (h - 1);
-        return (int)(t.b0 + c < t.bs ? c : t.bs - 1 - t.b0) * t.n + j;
-    };
-    float cx[NC], cy[NC];
-    {
-        const int co = co_of(lane);
-#pragma unroll
-        for (int m = 0; m < NC; ++m) {
-            cx[m] = -1.0f * ch0[co + m * hs];
-            cy[m] = -1.0f * ch0[co + h + m * hs];
-        }
-    }
-#pragma unroll 1
-    for (int idx = lane; idx < CPW * h; idx += 64) {
-        const int c = idx >> ls, j = idx & (h - 1);
-        const Cw w = t.cw(c);
-        float nx[NC], ny[NC];
-        if (idx + 64 < CPW * h) {
-            const int co = co_of(idx + 64);
-#pragma unroll
-            for (int m = 0; m < NC; ++m) {
-                nx[m] = -1.0f * ch0[co + m * hs];
-                ny[m] = -1.0f * ch0[co + h + m * hs];
-            }
-        }
-        vnode64<L, V, NS, FM>(t, w, cx, cy, wb, j, gmask, is_g, pos, ls);
-#pragma unroll
-        for (int m = 0; m < NC; ++m) {
-            cx[m] = nx[m];
-            cy[m] = ny[m];
-        }
-    }
-#else
 #pragma unroll 1
     for (int idx = lane, it = 0; idx < CPW * h; idx += 64, ++it) {
         const int c = idx >> ls, j = idx & (h - 1);
@@ -871,7 +673,6 @@ __device__ void vvisit64(const St& t, int pos, bool is_g, int lane, const int* w
         }
         vnode64<L, V, NS, FM>(t, w, cx, cy, wb, j, gmask, is_g, pos, ls, vc, it, w7);
     }
-#endif
 }
 
 // One pass of a virtual node for the exact f (FM = 1, any V >= 1), where an f costs ~65 VALU and
@@ -885,12 +686,6 @@ __device__ void vvisit64(const St& t, int pos, bool is_g, int lane, const int* w
 // chains over every entry.)  Level q (stage s + q) combines v[m] and v[m + 2^q], m < 2^q: f when
 // the stage-(s+q) node is a left child, else g with bit base[q] + m 2^s of the path.  The same
 // operands and operations as vtree(), so the same values.
-#ifndef PL_SCL_VPF
-#define PL_SCL_VPF 0  // 1: min-sum virtual passes load the next element's channel values ahead (A/B)
-#endif
-#ifndef PL_SCL_FEX_COMBO
-#define PL_SCL_FEX_COMBO 1  // 1: the f level after the first per-path g from its four path-independent outcomes
-#endif
 template <int Q, typename F>
 __device__ __forceinline__ void vex_levels(F& level) {  // level(Q), level(Q - 1), ..., level(0)
     if constexpr (Q >= 0) {
@@ -898,23 +693,13 @@ __device__ __forceinline__ void vex_levels(F& level) {  // level(Q), level(Q - 1
         vex_levels<Q - 1>(level);
     }
 }
-#ifndef PL_SCL_FEX_INL
-#define PL_SCL_FEX_INL 1  // 1: vvisit_ex inlined (its register blocks in the kernel's registers); 0: out of line (A/B r03i:
-                          // callee register saves through scratch every pass, 4.10 vs 3.71 ms)
-#endif
-#if PL_SCL_FEX_INL
-#define PL_FEX_PASS_ATTR __forceinline__
-#else
-#define PL_FEX_PASS_ATTR __noinline__
-#endif
 template <int L, int V, int CPW>
-__device__ PL_FEX_PASS_ATTR void vvisit_ex(const float* __restrict__ llr, int64_t b0, int64_t bs, int n, int W, int per,
-                                       double lmax, unsigned char* smem, int cw_bytes, int off_A, int off_beta,
-                                       int s, int pos, int is_g, int lane, const double* __restrict__ vcache,
-                                       VCache<1>* vc = nullptr, int off_sptr = 0) {
-    // Out of line with scalar arguments only: the pass's register arrays are allocated apart from
-    // the lane subtree's state (inlined, the two together spilled), and nothing goes through
-    // scratch but the call's own register saves, once per pass.
+__device__ __forceinline__ void vvisit_ex(const float* __restrict__ llr, int64_t b0, int64_t bs, int n, int W, int per,
+                                          double lmax, unsigned char* smem, int cw_bytes, int off_A, int off_beta,
+                                          int s, int pos, int is_g, int lane, const double* __restrict__ vcache,
+                                          VCache<1>* vc, int off_sptr) {
+    // Inlined: the pass's register blocks live in the kernel's registers.  Out of line, the callee's
+    // register saves went through scratch every pass (A/B r03i: 4.10 vs 3.71 ms).
     constexpr int NC = 1 << V, H = NC / 2;
     const int ls = s - 1, h = 1 << ls, hs = 1 << s;
     uint32_t gmask = 0u;  // level q is a g iff the stage-(s+q) node is a right child
@@ -938,7 +723,7 @@ __device__ PL_FEX_PASS_ATTR void vvisit_ex(const float* __restrict__ llr, int64_
     // path-independent sums (g with u = 0 or 1), so its four outcomes per element are computed
     // once and a path selects one by its two partial-sum bits -- 4 h2 f per side instead of h2 per
     // path (8 paths).  Same operands and operations as the per-path evaluation.
-    const bool combo = PL_SCL_FEX_COMBO && ns < V && q1 >= 1 && ((gmask >> (q1 - 1)) & 1u) == 0u;
+    const bool combo = ns < V && q1 >= 1 && ((gmask >> (q1 - 1)) & 1u) == 0u;
     typedef double wv __attribute__((ext_vector_type(NC)));
 #pragma unroll 1
     for (int idx = lane, it = 0; idx < CPW * h; idx += 64, ++it) {
@@ -948,7 +733,6 @@ __device__ PL_FEX_PASS_ATTR void vvisit_ex(const float* __restrict__ llr, int64_
         const uint32_t* beta = reinterpret_cast<const uint32_t*>(base + off_beta);
         if (vc != nullptr && is_g) {  // the right pass from the left pass's values (VCache)
             const uint8_t* sptr = base + off_sptr;
-#if PL_SCL_VC_BATCH
             constexpr int B = L <= 8 ? L : 1;  // paths per batch (wider lists: one, as before)
 #pragma unroll
             for (int p0 = 0; p0 < L; p0 += B) {
@@ -964,13 +748,6 @@ __device__ PL_FEX_PASS_ATTR void vvisit_ex(const float* __restrict__ llr, int64_
                     A[(p0 + q) * per + (1 << ls) - (1 << R) + j] =
                         g_op(xy[q].x, xy[q].y, (wd[q] >> ((pos + j) & 31)) & 1u);
             }
-#else
-#pragma unroll 1
-            for (int p = 0; p < L; ++p) {
-                const double2 xy = vc->v[it * L + sptr[p * SPS + s]];
-                A[p * per + (1 << ls) - (1 << R) + j] = g_op(xy.x, xy.y, getbit(beta + p * W, pos + j));
-            }
-#endif
             continue;
         }
         VEX_T0;
@@ -1139,7 +916,7 @@ __device__ PL_FEX_PASS_ATTR void vvisit_ex(const float* __restrict__ llr, int64_
                 const int ox = bx[Q] + jo, oy = by[Q] + jo;
                 // with the four-outcome step, a per-path f level lies at least two levels below
                 // the first per-path g (q1 <= V - 1): level V - 2 is always a g
-                if (((gmask >> Q) & 1u) || (PL_SCL_FEX_COMBO && Q > V - 3)) {
+                if (((gmask >> Q) & 1u) || Q > V - 3) {
 #pragma unroll
                     for (int m = 0; m < HQ; ++m) {
                         vx[m] = g_op(vx[m], vx[m + HQ], getbit(bp, ox + m * hs));
@@ -1175,7 +952,8 @@ __device__ PL_FEX_PASS_ATTR void vvisit_ex(const float* __restrict__ llr, int64_
 template <int L, int FM, int CPW, int LS>
 __device__ __forceinline__ void node_fg_st(const St& t, int pos, bool is_g, int lane) {
     constexpr int LL = ilog2(L), h = 1 << LS, total = CPW * L * h, IT = (total + 63) / 64;
-    constexpr int CH = IT < PL_SCL_ST_CH ? IT : PL_SCL_ST_CH;
+    constexpr int ST_CH = 8;  // elements per lane loaded ahead
+    constexpr int CH = IT < ST_CH ? IT : ST_CH;
     const int s = LS + 1;
     asm volatile("" : "+v"(lane));  // opaque per call: keeps the per-lane addresses from being
                                     // hoisted out of the decoder loop (they spilled the subtree)
@@ -1224,7 +1002,8 @@ __device__ void node_fg(const St& t, int s, int pos, bool is_g, int lane, VCache
 #endif
     if (PL_SCL_DIAG_SKIP_V && s > t.SS) {
     } else if (PL_SCL_DIAG_SKIP_ST && s <= t.SS) {
-    } else if (PL_SCL_ST_UNROLL && FM == 0 && s <= t.SS && ls <= R + 1) {  // exact f: spills (7.7 -> 11.2 ms)
+    } else if (FM == 0 && s <= t.SS && ls <= R + 1) {  // unrolled, loads first (A/B r02zk: 1.081 -> 1.050 ms;
+                                                       // exact f: spills, 7.7 -> 11.2 ms)
         if (ls == R) node_fg_st<L, FM, CPW, R>(t, pos, is_g, lane);
         else node_fg_st<L, FM, CPW, R + 1>(t, pos, is_g, lane);
     } else if (FM == 1 && s <= t.SS && !is_g && (CPW * L * h) % 128 == 0) {
@@ -1284,7 +1063,7 @@ __device__ void node_fg(const St& t, int s, int pos, bool is_g, int lane, VCache
                 case 3: vvisit64<L, V, 3, FM, CPW>(t, pos, is_g, lane, wb, gmask, vc); break;
                 default: vvisit64<L, V, 4, FM, CPW>(t, pos, is_g, lane, wb, gmask, vc); break;
             }
-        } else if constexpr (FM == 1 && V >= 1 && PL_SCL_FEX_HOIST) {
+        } else if constexpr (FM == 1 && V >= 1) {
             vvisit_ex<L, V, CPW>(t.llr, t.b0, t.bs, t.n, t.W, t.per, t.lmax, t.smem, t.y.bytes, t.y.off_A,
                                  t.y.off_beta, s, pos, is_g ? 1 : 0, lane, t.vcache, vc, t.y.off_sptr);
         } else {
@@ -1369,12 +1148,9 @@ constexpr int IDX(int s) { return (1 << s) - 1; }
 // rest, two at a time where it can: interleaved chains) and takes the other half from its partner
 // (lane ^ L) -- half the f evaluations of the lane subtree, whose values are unchanged.  MEM: the
 // input is the stage-R region in LDS, addressed per lane; otherwise registers, selected per lane.
-#ifndef PL_SCL_FEX_SPLIT
-#define PL_SCL_FEX_SPLIT 1
-#endif
 template <int h, int FM, int L, bool MEM>
 __device__ __forceinline__ void f_span(const double* in, double* out, double lmax) {
-    if constexpr (FM == 1 && h >= 2 && PL_SCL_FEX_SPLIT) {
+    if constexpr (FM == 1 && h >= 2) {
         constexpr int q = h / 2;
         const int lane = threadIdx.x;
         const bool hi = (lane & L) != 0;
@@ -1409,14 +1185,6 @@ __device__ __forceinline__ void f_span(const double* in, double* out, double lma
             out[j] = hi ? o : r[j];
             out[j + q] = hi ? r[j] : o;
         }
-    } else if constexpr (FM == 1 && h >= 2) {
-#pragma unroll
-        for (int j = 0; j < h; j += 2) {
-            double a, b;
-            f_ex2(in[j], in[j + h], in[j + 1], in[j + 1 + h], lmax, a, b);
-            out[j] = a;
-            out[j + 1] = b;
-        }
     } else {
 #pragma unroll
         for (int j = 0; j < h; ++j) out[j] = f_op<FM>(in[j], in[j + h], lmax);
@@ -1432,17 +1200,9 @@ __device__ __forceinline__ void f_down(double* st, double lmax) {
     }
 }
 
-__device__ __forceinline__ void load_group_fence(int j) {
-#if PL_SCL_LOADGRP > 0
-    if ((j + 1) % PL_SCL_LOADGRP == 0) __builtin_amdgcn_sched_barrier(0);
-#else
-    (void)j;
-#endif
-}
-
-// Leaf i (> 0) with tz = ctz(i) trailing zeros: g at stage tz+1 into stage tz, then f down.
-template <int tz, int FM, int L>
-__device__ __forceinline__ void g_step(const double* inA, double* st, uint32_t ps, int i, double lmax) {
+// g at stage tz+1 into stage tz for leaf i (> 0, tz = ctz(i)), without descending
+template <int tz>
+__device__ __forceinline__ void g_only(const double* inA, double* st, uint32_t ps, int i) {
     constexpr int h = 1 << tz;
     const int p0 = i - h;  // start of the left sibling, whose partial sums g consumes
 #pragma unroll
@@ -1456,28 +1216,14 @@ __device__ __forceinline__ void g_step(const double* inA, double* st, uint32_t p
             y = st[IDX(tz + 1) + j + h];
         }
         st[IDX(tz) + j] = g_op(x, y, (ps >> (p0 + j)) & 1u);
-        if constexpr (tz + 1 == R) load_group_fence(j);
     }
-    f_down<tz, FM, L>(st, lmax);
 }
 
-// g at stage tz+1 into stage tz for leaf i (tz = ctz(i)), without descending
-template <int tz>
-__device__ __forceinline__ void g_only(const double* inA, double* st, uint32_t ps, int i) {
-    constexpr int h = 1 << tz;
-    const int p0 = i - h;
-#pragma unroll
-    for (int j = 0; j < h; ++j) {
-        double x, y;
-        if constexpr (tz + 1 == R) {
-            x = inA[j];
-            y = inA[j + h];
-        } else {
-            x = st[IDX(tz + 1) + j];
-            y = st[IDX(tz + 1) + j + h];
-        }
-        st[IDX(tz) + j] = g_op(x, y, (ps >> (p0 + j)) & 1u);
-    }
+// ... then f down to the leaf
+template <int tz, int FM, int L>
+__device__ __forceinline__ void g_step(const double* inA, double* st, uint32_t ps, int i, double lmax) {
+    g_only<tz>(inA, st, ps, i);
+    f_down<tz, FM, L>(st, lmax);
 }
 
 template <int FM, int L>
@@ -1488,10 +1234,7 @@ __device__ __forceinline__ void leaf_llr(const double* inA, double* st, uint32_t
             f_span<h, FM, L, true>(inA, st + IDX(R - 1), lmax);
         } else {
 #pragma unroll
-            for (int j = 0; j < h; ++j) {
-                st[IDX(R - 1) + j] = f_op<FM>(inA[j], inA[j + h], lmax);
-                load_group_fence(j);
-            }
+            for (int j = 0; j < h; ++j) st[IDX(R - 1) + j] = f_op<FM>(inA[j], inA[j + h], lmax);
         }
         f_down<R - 1, FM, L>(st, lmax);
         return;
@@ -1517,94 +1260,25 @@ __device__ __forceinline__ void pull_live(double* st, int i, int src) {
     }
 }
 
-// Selection by push (2L = 16): every candidate lane holds the whole state of its path (path and
-// shadow lanes mirror each other), so after ranking it sends that state -- metric, partial sums
+// Selection by push (2L = 16: the L = 8 min-sum information leaves of subtree(), and select_2l's
+// permute for the other selections at L = 8).  Every candidate lane holds the whole state of its
+// path (path and shadow lanes mirror each other), so it sends that state -- metric, partial sums
 // with its own bit, origin and the live stage buffers -- straight to the group lane of its rank
 // with ds_permute, and each shadow lane L..2L-1 then copies its path lane (gl - L) in one DPP row
 // rotation by L restricted to the upper banks.  One LDS round trip per information leaf instead of
-// three (push the parent code, copy it to the shadows, pull the parent's state); the same values.
-// A/B r04r (min-sum, L = 8): 0.858 vs 0.864 ms.
-#ifndef PL_SCL_PUSH
-#define PL_SCL_PUSH 1
-#endif
-#ifndef PL_SCL_PUSH_DPERM
-#define PL_SCL_PUSH_DPERM 0  // 1: the shadow copies by a second ds_permute to slot (rank + L) mod 2L instead of DPP
-#endif
-template <int L>
-__device__ __forceinline__ int push_i(int v, int dst) {
-    static_assert(L == 8, "push selection: 2L = 16 (one DPP row per codeword)");
-#if PL_SCL_PUSH_DPERM
-    // dst2 = the group lane L slots away (a permutation too): slot >= L receives the candidate of
-    // rank slot - L, its path lane's
-    const int dst2 = dst ^ (L << 2);
-    const int r = __builtin_amdgcn_ds_permute(dst, v), r2 = __builtin_amdgcn_ds_permute(dst2, v);
-    return (threadIdx.x & L) ? r2 : r;
-#else
-    const int r = __builtin_amdgcn_ds_permute(dst, v);
-    return __builtin_amdgcn_update_dpp(r, r, 0x120 + L, 0xF, 0xC, false);  // row_ror:8, lanes 8..15 of each row
-#endif
-}
-template <int L>
-__device__ __forceinline__ double push_d(double v, int dst) {
-    const long long b = __double_as_longlong(v);
-    const int lo = push_i<L>((int)(b & 0xffffffffLL), dst), hi = push_i<L>((int)(b >> 32), dst);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// A live stage-s buffer whose parent stage s+1 is live too is the f of the parent's (its node is
-// the left child, and neither buffer has changed since the node began): it is recomputed from the
-// moved parent instead of moved (PL_SCL_PUSH_REFM), which halves the values moved per information
-// leaf on average (4 doubles instead of 7); the same f, so the same values (A/B r04v: 0.847 vs 0.850 ms).
-#ifndef PL_SCL_PUSH_REFM
-#define PL_SCL_PUSH_REFM 1
-#endif
-// PL_SCL_PUSH == 2: one ds_permute sends each candidate's lane index to the slot of its rank, a
-// DPP row rotation gives the shadow slots their path slot's source, and every value is then pulled
-// (ds_bpermute) from that source lane -- two round trips, one forward permute (A/B r04x: 0.848
-// vs 0.850 ms, within noise; a second forward permute for the shadows instead of the DPP copy,
-// PL_SCL_PUSH_DPERM: 0.989 ms).
-template <int L>
-__device__ __forceinline__ int pull_src(int gl_lane, int dst) {
-    const int r = __builtin_amdgcn_ds_permute(dst, gl_lane);
-    return __builtin_amdgcn_update_dpp(r, r, 0x120 + L, 0xF, 0xC, false);
-}
-template <int L, int FM, int s>
-__device__ __forceinline__ void pull2_live(double* st, int i, int src, double lmax) {
-    if constexpr (s >= 1) {
-        if (((i >> (s - 1)) & 1) == 0) {
-            if (PL_SCL_PUSH_REFM && s + 1 < R && ((i >> s) & 1) == 0) {
-                constexpr int h = 1 << s, sp = s + 1 < R ? s + 1 : s;
-#pragma unroll
-                for (int j = 0; j < h; ++j) st[IDX(s) + j] = f_op<FM>(st[IDX(sp) + j], st[IDX(sp) + j + h], lmax);
-            } else {
-#pragma unroll
-                for (int j = 0; j < (1 << s); ++j) st[IDX(s) + j] = bperm_d(st[IDX(s) + j], src);
-            }
-        }
-        pull2_live<L, FM, s - 1>(st, i, src, lmax);
-    }
-}
-template <int L, int FM, int s>
-__device__ __forceinline__ void push_live(double* st, int i, int dst, double lmax) {
-    if constexpr (s >= 1) {
-        if (((i >> (s - 1)) & 1) == 0) {
-            if (PL_SCL_PUSH_REFM && s + 1 < R && ((i >> s) & 1) == 0) {
-                constexpr int h = 1 << s, sp = s + 1 < R ? s + 1 : s;
-#pragma unroll
-                for (int j = 0; j < h; ++j) st[IDX(s) + j] = f_op<FM>(st[IDX(sp) + j], st[IDX(sp) + j + h], lmax);
-            } else {
-#pragma unroll
-                for (int j = 0; j < (1 << s); ++j) st[IDX(s) + j] = push_d<L>(st[IDX(s) + j], dst);
-            }
-        }
-        push_live<L, FM, s - 1>(st, i, dst, lmax);
-    }
-}
-
-// Selection by speculative push (PL_SCL_SPEC; 2L = 16: the L = 8 min-sum push above, and
-// select_2l's permute for the exact-f and fast-SCL kernels).  The push waits for the rank; the
-// round-5 rank from the metrics' high words also waited for its permutation check -- a chain of
-// five DPP ORs, a compare and a wave-uniform branch between the rank and the first ds_permute,
-// ~0.04 ms of the bench kernel on its own (r05w_scl_fb2_ab.txt).  Here the rank is taken on a
+// three (push the parent code, copy it to the shadows, pull the parent's state); the same values
+// (A/B r04r, min-sum, L = 8: 0.858 vs 0.864 ms; pulling every value from a pushed source lane
+// instead, r04x: 0.848 vs 0.850 ms, within noise; the shadow copies by a second ds_permute
+// instead of the DPP copy: 0.989 ms).  A live stage-s buffer whose parent stage s+1 is live too is
+// the f of the parent's (its node is the left child, and neither buffer has changed since the node
+// began): it is recomputed from the moved parent instead of moved, which halves the values moved
+// per information leaf on average (4 doubles instead of 7); the same f, so the same values (A/B
+// r04v: 0.847 vs 0.850 ms).
+//
+// The push is speculative.  A push by the full 64-bit rank waits for it, and the round-5 rank from
+// the metrics' high words also waited for its permutation check -- a chain of five DPP ORs, a
+// compare and a wave-uniform branch between the rank and the first ds_permute, ~0.04 ms of the
+// bench kernel on its own (r05w_scl_fb2_ab.txt).  Here the rank is taken on a
 // 32-bit key that is UNIQUE in the row, so it is always a permutation and every candidate is pushed
 // at once; the order is checked afterwards, on the pushed metrics, while the other pushes are
 // still in flight (same-process A/B on the bench's AWGN input, profiles/r06a/r06b_scl_spec_ab*.txt:
@@ -1620,11 +1294,9 @@ __device__ __forceinline__ void push_live(double* st, int i, int dst, double lma
 //     row shift per word): equal keys are in index order, so equal metrics are too;
 //   * if any row of the wave fails, the pushed candidates are ranked again by the full 64-bit
 //     stable rank (rank16_subb, the slot as the index -- equal metrics are in candidate order in
-//     the slots) and pushed once more; then the shadow slots copy their path slot as before.
-// Same selection, same values as the other forms (every SCL parity test runs this kernel).
-#ifndef PL_SCL_SPEC
-#define PL_SCL_SPEC 1
-#endif
+//     the slots) and pushed once more; then the shadow slots copy their path slot.
+// Same selection, same values as the rank-then-pull form of the other list sizes (every SCL parity
+// test runs this kernel).
 __device__ __forceinline__ uint32_t rank_key16(double cv, int gl) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(cv);
     // bits 57..26 of the metric's bits minus 979 << 52: in range (2^-44 <= metric < 2^20) the 6
@@ -1681,29 +1353,28 @@ __device__ __forceinline__ bool row_order_ok(double p) {
     return (((unsigned long long)phi << 32) | plo) <= b;
 }
 // some row of the wave is out of order (rare: taken out of line)
-#if PL_DEV && defined(PL_SCL_DIAG_SPEC_FB)  // 1 = always re-rank the pushed candidates (same results), 2 = never (timing)
-#define PL_SPEC_REDO(p) \
-    (PL_SCL_DIAG_SPEC_FB == 1 || (PL_SCL_DIAG_SPEC_FB == 0 && __builtin_amdgcn_ballot_w64(!row_order_ok(p)) != 0))
+#if PL_SCL_DIAG_SPEC_FB  // 1 = always re-rank the pushed candidates (same results), 2 = never (timing)
+#define PL_SPEC_REDO(p) (PL_SCL_DIAG_SPEC_FB == 1)
 #else
 #define PL_SPEC_REDO(p) __builtin_expect(__builtin_amdgcn_ballot_w64(!row_order_ok(p)) != 0, 0)
 #endif
-// the moved live buffers (those push_live moves), without the shadow copy
+// the moved live buffers (those not recomputed from their moved parent), without the shadow copy
 template <int s>
 __device__ __forceinline__ void push_live_raw(double* st, int i, int dst) {
     if constexpr (s >= 1) {
-        if (((i >> (s - 1)) & 1) == 0 && !(PL_SCL_PUSH_REFM && s + 1 < R && ((i >> s) & 1) == 0)) {
+        if (((i >> (s - 1)) & 1) == 0 && !(s + 1 < R && ((i >> s) & 1) == 0)) {
 #pragma unroll
             for (int j = 0; j < (1 << s); ++j) st[IDX(s) + j] = push_raw_d(st[IDX(s) + j], dst);
         }
         push_live_raw<s - 1>(st, i, dst);
     }
 }
-// the shadow copies of the moved live buffers, then the recomputed ones (push_live's order)
+// the shadow copies of the moved live buffers and the recomputed ones, from the top stage down
 template <int L, int FM, int s>
 __device__ __forceinline__ void reshadow_live(double* st, int i, double lmax) {
     if constexpr (s >= 1) {
         if (((i >> (s - 1)) & 1) == 0) {
-            if (PL_SCL_PUSH_REFM && s + 1 < R && ((i >> s) & 1) == 0) {
+            if (s + 1 < R && ((i >> s) & 1) == 0) {
                 constexpr int h = 1 << s, sp = s + 1 < R ? s + 1 : s;
 #pragma unroll
                 for (int j = 0; j < h; ++j) st[IDX(s) + j] = f_op<FM>(st[IDX(sp) + j], st[IDX(sp) + j + h], lmax);
@@ -1722,27 +1393,24 @@ __device__ __forceinline__ void reshadow_live(double* st, int i, double lmax) {
 // candidate to the group lane of its rank (ranks are a permutation of [0, 2L), so every lane is
 // written exactly once), and slots >= L re-shadow slot - L.  Returns the lane's new metric, the
 // path (group index) it descends from and the bit the candidate appended.
-template <int L, int FM>
+template <int L>
 __device__ __forceinline__ int rank_2l(double cv, int gl, int lane) {
+#if PL_SCL_DIAG_NO_RANK  // timing diagnostic only (wrong selection)
+    return gl;
+#else
     constexpr int GW = 2 * L;
     int rk = 0;
-#if PL_SCL_DIAG_NO_RANK  // timing diagnostic only (wrong selection)
-    if (true) {
-        rk = gl;
-    } else
-#endif
     if constexpr (GW == 64) {
 #pragma unroll
         for (int c = 0; c < 2 * L; ++c) {
             const double v = readlane_d(cv, c);
             rk += (v < cv || (v == cv && c < lane)) ? 1 : 0;
         }
-    } else if constexpr (GW == 16 && FM == 0 && PL_SCL_RANK_SUBB && PL_SCL_RANK_SPLIT) {
-        rk = rank16_split(cv);  // min-sum kernels only: its 14 mask SGPRs spill the exact-f ones
     } else {
         rank_rot<GW, 1>(cv, gl, lane, rk);
     }
     return rk;
+#endif
 }
 template <int L, int FM>
 __device__ __forceinline__ void select_2l(double cv, int gl, int gbase, int lane, double& npm, int& par,
@@ -1750,11 +1418,7 @@ __device__ __forceinline__ void select_2l(double cv, int gl, int gbase, int lane
     const bool hi = (gl & L) != 0;
     const int code = (gl & (L - 1)) | (hi ? 256 : 0);
     int rcode, rlo, rhi;
-#if PL_SCL_DIAG_NO_RANK
-    if constexpr (false) {
-#else
-    if constexpr (PL_SCL_SPEC && 2 * L == 16) {
-#endif
+    if constexpr (2 * L == 16 && !PL_SCL_DIAG_NO_RANK) {
         // the speculative form of the push selection (rank16_key, row_order_ok): candidates go to
         // the slot of their key rank at once, and a misordered row re-ranks the pushed candidates
         const int dst = (gbase + rank16_key(rank_key16(cv, gl))) << 2;
@@ -1769,7 +1433,7 @@ __device__ __forceinline__ void select_2l(double cv, int gl, int gbase, int lane
         rlo = (int)(pb & 0xffffffffLL);
         rhi = (int)(pb >> 32);
     } else {
-        const int dst = gbase + rank_2l<L, FM>(cv, gl, lane);
+        const int dst = gbase + rank_2l<L>(cv, gl, lane);
         const long long cb = __double_as_longlong(cv);
         rcode = __builtin_amdgcn_ds_permute(dst << 2, code);
         rlo = __builtin_amdgcn_ds_permute(dst << 2, (int)(cb & 0xffffffffLL));
@@ -1868,7 +1532,7 @@ __device__ void subtree(const St& t, int i0, uint32_t fz, double& pm, int& org, 
     // which left every leaf-index shift, combine and g stage a run-time choice
     auto leaf = [&](const int i) __attribute__((always_inline)) {
         if (FAST && i < resume) return;
-        if (!FAST && PL_SCL_FROZEN_PAIR && (i & 1) && pair) return;  // done with leaf i-1
+        if (!FAST && (i & 1) && pair) return;  // done with leaf i-1
         if (i > 0) {  // nodes that ended at leaf i-1 (stages 1..ctz(i)): [uL ^ uR, uR] (:147-153)
             const int tz = __builtin_ctz(i);
             for (int s = 1; s <= tz; ++s) {
@@ -1934,7 +1598,7 @@ __device__ void subtree(const St& t, int i0, uint32_t fz, double& pm, int& org, 
         // shadow lanes take leaf i+1's LLR g(a, b, 0) from the stage-1 input and the pair costs
         // one exp/log per lane; the metric still adds the two terms in order.
         double lv = st[0];
-        if constexpr (!FAST && PL_SCL_FROZEN_PAIR) {
+        if constexpr (!FAST) {
             pair = (i & 1) == 0 && ((fz >> i) & 3u) == 3u;
             if (pair && hi) lv = g_op(st[IDX(1)], st[IDX(1) + 1], 0u);
         }
@@ -1950,7 +1614,7 @@ __device__ void subtree(const St& t, int i0, uint32_t fz, double& pm, int& org, 
         const double pen = pl::softplus_pm(-sl);
 #endif
         if (!info) {  // frozen leaf: metric update only (u = 0)
-            if (!FAST && PL_SCL_FROZEN_PAIR && pair) {
+            if (!FAST && pair) {
                 const double oth = half_xchg<L>(pen, lane);
                 pm = (pm + (hi ? oth : pen)) + (hi ? pen : oth);
             } else {
@@ -1963,7 +1627,7 @@ __device__ void subtree(const St& t, int i0, uint32_t fz, double& pm, int& org, 
         asm volatile("" ::"v"(pen));
         PROF_MARK(9);
 #endif
-        if constexpr (PL_SCL_SPEC && PL_SCL_PUSH == 1 && L == 8 && FM == 0 && !PL_SCL_DIAG_NO_PULL) {
+        if constexpr (L == 8 && FM == 0 && !PL_SCL_DIAG_NO_PULL) {  // the speculative push (exact f: spills, r04r)
             const double cv = pm + pen;
             const int dst = (gbase + rank16_key(rank_key16(cv, gl))) << 2;
             double p = push_raw_d(cv, dst);
@@ -1990,35 +1654,6 @@ __device__ void subtree(const St& t, int i0, uint32_t fz, double& pm, int& org, 
 #endif
             return;
         }
-        if constexpr (PL_SCL_PUSH == 2 && L == 8 && FM == 0 && !PL_SCL_DIAG_NO_PULL) {
-            const double cv = pm + pen;
-            const int dst = (gbase + rank_2l<L, FM>(cv, gl, lane)) << 2;
-            const int src = pull_src<L>(lane, dst);
-            pm = bperm_d(cv, src);
-            ps = (uint32_t)bperm_i((int)(ps | ((hi ? 1u : 0u) << i)), src);
-            org = bperm_i(org, src);
-            inA = w.A + org * t.per;
-            pull2_live<L, FM, R - 1>(st, i, src, t.lmax);
-            return;
-        }
-        if constexpr (PL_SCL_PUSH == 1 && L == 8 && FM == 0 && !PL_SCL_DIAG_NO_PULL) {  // exact f: spills (r04r)
-            const double cv = pm + pen;
-            const int dst = (gbase + rank_2l<L, FM>(cv, gl, lane)) << 2;
-#if PL_SCL_PROF
-            asm volatile("" ::"v"(dst));
-            PROF_MARK(10);
-#endif
-            pm = push_d<L>(cv, dst);
-            ps = (uint32_t)push_i<L>((int)(ps | ((hi ? 1u : 0u) << i)), dst);
-            org = push_i<L>(org, dst);
-            inA = w.A + org * t.per;
-            push_live<L, FM, R - 1>(st, i, dst, t.lmax);
-#if PL_SCL_PROF
-            asm volatile("" ::"v"(pm), "v"(ps), "v"(org));
-            PROF_MARK(11);
-#endif
-            return;
-        }
         double npm;
         int par;
         uint32_t bit;
@@ -2031,7 +1666,8 @@ __device__ void subtree(const St& t, int i0, uint32_t fz, double& pm, int& org, 
         pull_live<R - 1>(st, i, gbase + par);
 #endif
     };
-    if constexpr (!FAST && PL_SCL_UNROLL) {
+    if constexpr (!FAST) {  // A/B: 2.08 vs 2.27 ms; with constant leaf indices (round 6): 0.793 -> 0.744 ms,
+                            // profiles/r06d_scl_unroll_ab.txt
         unroll_leaves(leaf, std::make_integer_sequence<int, T>{});
     } else {
 #pragma unroll
@@ -2114,7 +1750,6 @@ __device__ __forceinline__ int node_kind(const uint32_t* __restrict__ fw, int s,
 template <int L, int V, int CPW>
 __device__ void repoint(const St& t, int i0, int lane) {
     constexpr int LL = ilog2(L);
-#if PL_SCL_REPOINT_VEC
     if (V >= 2 || t.W >= 4) {  // V >= 2: n >= 128, so W >= 4 (the word loop below is not compiled in)
         // LPP = 64 / (CPW * L) lanes per (codeword, path) pair (2 at CPW * L = 32, 4 with two rows
         // per codeword): one origin load each, the pair's partial-sum row in 16-byte quads (words
@@ -2145,8 +1780,7 @@ __device__ void repoint(const St& t, int i0, int lane) {
         __syncthreads();
         return;
     }
-#endif
-    if constexpr (PL_SCL_REPOINT_VEC && V >= 2) return;
+    if constexpr (V >= 2) return;
     const int W = t.W, w_lim = (i0 + 31) >> 5;
     // CPW * L = 32 (codeword, path) pairs per wave, <= 32 words each (n <= 1024)
     constexpr int RB = 32 * 32 / 64;
@@ -2223,9 +1857,7 @@ __device__ void upper_prune(const St& t, int s, int pos, int kind, double& pm, i
 
 template <int L, int V, int FM, bool FAST>
 __global__ __launch_bounds__(64)
-#if PL_SCL_WPE > 0
-__attribute__((amdgpu_waves_per_eu(PL_SCL_WPE)))
-#endif
+__attribute__((amdgpu_waves_per_eu(2)))  // <= 256 VGPRs (A/B on MI355X: 2.30 vs 3.62 ms at V = 4 without)
 void scl_tree_kernel(const float* __restrict__ llr, int64_t bs, void* __restrict__ out,
                                                       int out_kind, double* __restrict__ out_pm,
                                                       const uint32_t* __restrict__ frozen_words,
@@ -2305,7 +1937,6 @@ void scl_tree_kernel(const float* __restrict__ llr, int64_t bs, void* __restrict
                 __threadfence_block();
                 __syncthreads();
             }
-#if PL_SCL_FEX_COMBO
 #pragma unroll 1
             for (int ns = 0; ns + 2 <= V; ++ns) {  // the four-outcome tables (combo_off)
                 const int D = n >> (ns + 2), lsz = S - ns - 2;
@@ -2342,17 +1973,13 @@ void scl_tree_kernel(const float* __restrict__ llr, int64_t bs, void* __restrict
             }
             __threadfence_block();
             __syncthreads();
-#endif
         }
     }
 
     PROF_MARK(6);
     VCache<FM> vcache_lane;  // the virtual-node cache (vnode64, vvisit_ex)
-#if PL_SCL_C7
     if constexpr (FM == 0) vcache_lane.p7 = -1;
-#endif
-    VCache<FM>* vcp = (PL_SCL_VCACHE && !PL_SCL_VPF && ((FM == 0 && V == 4) || (FM == 1 && V >= 1 && PL_SCL_FEX_HOIST)))
-                      ? &vcache_lane : nullptr;
+    VCache<FM>* vcp = ((FM == 0 && V == 4) || (FM == 1 && V >= 1)) ? &vcache_lane : nullptr;
     double pm = gl == 0 || gl == L ? 0.0 : lmax;  // :192-194 ([0, 30 x (L-1)] per half)
     const int nsub = n >> R;
     int q = 0;

@@ -297,6 +297,35 @@ def test_diagnostic_macros_refuse_release_builds(tmp_path):
         assert r.returncode != 0 and "development builds" in r.stderr, (src, r.stderr[-500:])
 
 
+def test_scl_development_macros_compile():
+    """The development-only paths of the SCL subtree kernel -- every PL_SCL_DIAG_* ablation and the
+    phase timing PL_SCL_PROF = 1, 2 -- still compile for gfx950 (no build compiles them otherwise:
+    tools/scl_variants.py and tools/scl_prof.py pass these macros by hand)."""
+    import re
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    from polar_amd import build as b
+    hipcc = b._hipcc()
+    path = os.path.join(b.CSRC, "scl_tree_kernel.hip")
+    src = open(path).read()
+    diag = sorted(set(re.findall(r"\bPL_SCL_DIAG_[A-Z0-9_]+\b", src)))
+    defaults = set(re.findall(r"^#define (PL_SCL_DIAG_[A-Z0-9_]+) 0\b", src, re.M))
+    assert set(diag) == defaults, set(diag) ^ defaults  # every ablation has its default in the block at the top
+    assert {"PL_SCL_DIAG_SKIP_V", "PL_SCL_DIAG_NO_RANK", "PL_SCL_DIAG_FMS_ALL", "PL_SCL_DIAG_SPEC_FB"} <= defaults
+    guard = re.search(r"#if !PL_DEV && \((.*?)\)\n#error", src, re.S).group(1)
+    assert set(re.findall(r"PL_SCL_DIAG_[A-Z0-9_]+", guard)) == defaults  # none reaches a release build
+    macros = [f"{m}=1" for m in diag] + ["PL_SCL_DIAG_SPEC_FB=2", "PL_SCL_PROF=1", "PL_SCL_PROF=2"]
+
+    def one(macro):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only",
+                            "-DPL_DEV=1", "-DPL_SCL_TREE_L=8", f"-D{macro}", path],
+                           capture_output=True, text=True, timeout=600)
+        return macro, r.returncode, r.stderr[-600:]
+    with ThreadPoolExecutor(8) as ex:
+        bad = [(m, e) for m, rc, e in ex.map(one, macros) if rc]
+    assert not bad, bad[:2]
+
+
 def test_bench_valu_roofline_from_committed_counters():
     """bench.py's VALU-issue roofline: from profiles/valu.json (per-class SQ counters x calibrated
     issue costs), current while the profiled instruction stream is the pinned one, reported null

@@ -5,7 +5,9 @@
 
 Prints, per phase of the decoder loop (scl_tree_kernel.hip, PL_SCL_PROF), the mean cycles per wave,
 the share of the sum, and the decode time of the same launch without instrumentation (default
-library) for scale.
+library) for scale.  Further variants (--flags NAME:-D...) take the development macros the source
+still has (PL_SCL_DIAG_*); an A/B of a new alternative adds its switch locally for the experiment
+and removes it when the decision is made.
 """
 import argparse
 import ctypes

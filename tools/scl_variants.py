@@ -1,9 +1,11 @@
 """Development aid: build SCL subtree-kernel variants (-D flags, L = 8 only) and time them in ONE
 process on the GPU against the default library.
 
-  python tools/scl_variants.py build NAME:"-DPL_SCL_R=4" ...     (build container; hipcc)
+  python tools/scl_variants.py build NAME:"-DPL_SCL_DIAG_NO_COMBINE=1" ...     (build container; hipcc)
   python tools/scl_variants.py time [--n 1024 --k 512 --bs 8192]   (GPU box)
 Variant libraries go to polar-code-pytorch-sionna_amd/polar_amd/_variants/ (git-ignored).
+The kernel source keeps no switch for a settled decision: an A/B adds its switch locally for the
+experiment and removes it when the decision is made.
 Environment knobs read at launch (PL_SCL_VIRTUAL=<max virtual stages>) apply to every library.
 """
 import ctypes
