@@ -23,6 +23,9 @@
  *   pl_plan_info / pl_plan_device: the plan's n, k, list size (polar_sc.py:14-17) and device
  *   pl_scl_decode    SCL_Dec.forward   x_run_sn_polar/polar/polar_scl.py:210-234
  *                    (+ final sorted msg_pm of _decode_np_batch :178-209)
+ *   pl_hybrid_decode SCL_Dec(use_hybrid_sc=True).forward my_sn/fec/polar/dec.py:187, :497-498 (a stub
+ *                    there: "not implement..."; the decoder its docstring cites)
+ *   pl_crc_status    SCL_Dec(return_crc_status=True) my_sn/fec/polar/dec.py:534-535 (a stub there)
  *   pl_polar_encode  PolarEncoder.forward x_run_sn_polar/polar/enc.py:30-43
  *                    (butterfly form of my_sn/fec/polar/enc.py:85-96)
  *   pl_crc_attach    CRCEncoder.forward my_sn/fec/crc.py:85-104 (G-matrix CRC, 5G polynomials :38-52)
@@ -123,6 +126,37 @@ int pl_polar_encode(const pl_plan* plan, const float* u_bits, int64_t bs, float*
  * dec.py:517) before the first argmin.  degree 0 turns it off.
  * Call before the plan's first decode.  Replaces SCL_Dec(crc_degree=...) (dec.py:210-218). */
 int pl_plan_set_crc(pl_plan* plan, int32_t degree, uint32_t poly_mask);
+
+/* Hybrid SC / SC-list decoding ([Cammerer_Hybrid_SCL]; SCL_Dec(use_hybrid_sc=True), which the
+ * reference names and never implemented, my_sn/fec/polar/dec.py:187, :497-498): SC-decode every row
+ * with sc_plan, list-decode with scl_plan only the rows whose SC result fails scl_plan's CRC.
+ *   u_sc = SC(llr); ok = crc_valid(u_sc); rows = ascending indices where !ok;
+ *   out = u_sc, out[rows] = SCL_crc(llr[rows]) exactly as pl_scl_decode decodes those rows;
+ *   crc_ok = ok, crc_ok[rows] = crc_valid(out[rows]).
+ * Not the same decoder as pure CRC-aided SCL: a row whose SC result passes the CRC keeps it, even
+ * where the list decoder would pick another CRC-valid word.
+ * sc_plan: list size 1; scl_plan: list size >= 2 with a CRC (pl_plan_set_crc; PL_ENOTSUP without);
+ * both of the same n, k and frozen set and on the same device (PL_EINVAL otherwise).  Each plan
+ * decodes with its own f mode, llr_max and kernel.
+ * crc_ok (nullable): device [bs] bytes, 1 = the row's output passes the CRC.  list_rows (nullable):
+ * device [bs] int32, its first *n_list entries receive the list-decoded rows, ascending.  n_list
+ * (nullable): HOST pointer, their number.
+ * workspace: device scratch of pl_hybrid_workspace_size(sc_plan, scl_plan, bs) bytes, required
+ * (NULL or a smaller one is PL_EINVAL): 5 bytes per row for the flags and the row list, and one
+ * chunk of min(bs, 16384) rows of LLRs, bits and the list plan's own workspace -- the failing rows
+ * are gathered and list-decoded in chunks of that size, so this part does not grow with bs.
+ * The call SYNCHRONISES its stream once: the number of failing rows sizes the list launches, so it
+ * is read back (8 bytes) after the SC stage.  For the same reason it cannot be captured into a HIP
+ * graph: on a capturing stream it returns PL_ENOTSUP before it touches the stream.  bs == 0 is PL_OK.
+ * pl_crc_status: valid[b] = 1 iff the k bits of row b of bits ([bs, k], kind PL_OUT_F32 / PL_OUT_U8)
+ * pass the plan's CRC (the last crc degree bits are the parity of the others), else 0; device [bs]
+ * bytes.  PL_ENOTSUP for a plan without a CRC. */
+size_t pl_hybrid_workspace_size(const pl_plan* sc_plan, const pl_plan* scl_plan, int64_t bs);
+int pl_hybrid_decode(const pl_plan* sc_plan, const pl_plan* scl_plan, const float* llr_logits, int64_t bs,
+                     void* out_bits, int32_t out_kind, uint8_t* crc_ok, int32_t* list_rows, int64_t* n_list,
+                     void* workspace, size_t ws_bytes, void* hip_stream);
+int pl_crc_status(const pl_plan* plan, const void* bits, int32_t kind, int64_t bs, uint8_t* valid,
+                  void* hip_stream);
 
 /* Which kernel a plan launches: *kind = PL_KERNEL_GENERIC / PL_KERNEL_SPECIALIZED (SC plans) or
  * PL_KERNEL_GENERIC / PL_KERNEL_SCL_SUBTREE (SCL plans; PL_PLAN_GENERIC or PL_SCL_TREE=0 in the

@@ -62,13 +62,18 @@ def _declare(L):
     L.pl_sc_sim_count.argtypes = [P, ctypes.c_uint64, ctypes.c_uint64, i64, i64, ctypes.c_float, P, P,
                                   ctypes.c_size_t, P, P, P]
     L.pl_clock_probe.argtypes = [P, i32, P]
+    L.pl_hybrid_workspace_size.argtypes = [P, P, i64]
+    L.pl_hybrid_workspace_size.restype = ctypes.c_size_t
+    L.pl_hybrid_decode.argtypes = [P, P, P, i64, P, i32, P, P, ctypes.POINTER(i64), P, ctypes.c_size_t, P]
+    L.pl_crc_status.argtypes = [P, P, i32, i64, P, P]
     L.pl_last_error_string.restype = ctypes.c_char_p
     L.pl_version.restype = ctypes.c_char_p
     for f in (L.pl_plan_create, L.pl_plan_destroy, L.pl_plan_info, L.pl_plan_device, L.pl_sc_decode, L.pl_scl_decode,
               L.pl_polar_encode, L.pl_plan_kernel, L.pl_sc_specialize, L.pl_sc_source, L.pl_plan_set_crc,
               L.pl_crc_attach, L.pl_crc_check,
               L.pl_gather_rows, L.pl_rate_recover, L.pl_awgn_qpsk_llr, L.pl_count_errors,
-              L.pl_awgn_qpsk_llr_bits, L.pl_sc_decode_count, L.pl_sc_sim_count, L.pl_clock_probe):
+              L.pl_awgn_qpsk_llr_bits, L.pl_sc_decode_count, L.pl_sc_sim_count, L.pl_clock_probe,
+              L.pl_hybrid_decode, L.pl_crc_status):
         f.restype = ctypes.c_int
     return L
 
@@ -105,14 +110,20 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_crc_check", "pl_gather_rows",
                     "pl_rate_recover", "pl_awgn_qpsk_llr", "pl_count_errors", "pl_awgn_qpsk_llr_bits",
                     "pl_sc_count_workspace_size", "pl_sc_decode_count", "pl_sc_sim_count", "pl_clock_probe",
+                    "pl_hybrid_workspace_size", "pl_hybrid_decode", "pl_crc_status",
                     "pl_last_error_string", "pl_version")
+
+
+class PolarArgumentError(PolarLibError, ValueError):
+    """PL_EINVAL: a ValueError, as bad arguments are everywhere in the package, that also carries
+    the return code like every other failed C-ABI call."""
 
 
 def check(rc, what):
     if rc != PL_OK:
         msg = lib().pl_last_error_string().decode(errors="replace")
         if rc == PL_EINVAL:
-            raise ValueError(f"{what}: {msg}")
+            raise PolarArgumentError(f"{what}: {msg}", rc)
         raise PolarLibError(f"{what} failed ({rc}): {msg}", rc)
 
 

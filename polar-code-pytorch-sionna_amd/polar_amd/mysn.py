@@ -12,8 +12,14 @@ they exist:
   * The reference's CRCEncoder cannot be constructed as shipped (crc.py:81 reads self.device,
     which is never set), so SCL_Dec(crc_degree=...) raises there; here it works, with the CRC of
     crc.py (pinned by tests/golden/crc.npz, generated with that one attribute set at run time).
-  * use_hybrid_sc and return_crc_status raise NotImplementedError, as the reference does
-    ("not implement...", dec.py:497-498, :534-535).
+  * use_hybrid_sc and return_crc_status work here; the reference raises "not implement..." for
+    both (dec.py:497-498, :534-535).  use_hybrid_sc=True is the decoder the reference's docstring
+    cites ([Cammerer_Hybrid_SCL]): exact-f SC on every row, the list decoder only on the rows whose
+    SC result fails the CRC (pl_hybrid_decode).  It is not pure CRC-aided SCL: a row whose SC
+    result passes the CRC keeps it, even where the list decoder would pick another CRC-valid
+    word.  msg_pm is None after a hybrid forward (rows SC decoded have no list) and
+    last_list_rows is the number of rows the last forward list-decoded.  return_crc_status=True
+    returns (u_hat, crc_status), crc_status torch.bool of shape input_shape[:-1].
   * Path-metric ties are broken in the stable (metric, index) order (the reference's np.argsort is
     unstable and host-dependent, see polar_scl.py notes in DESIGN.md §4).
 """
@@ -99,7 +105,9 @@ class SCL_Dec(nn.Module):
         assert np.log2(n) == int(np.log2(n)), "n must be a power of 2."
         assert np.log2(list_size) == int(np.log2(list_size)), "list_size must be a power of 2."
         self._use_fast_scl = bool(use_fast_scl)
-        self._use_hybrid_sc = False
+        self._use_hybrid_sc = bool(use_hybrid_sc)
+        if self._use_hybrid_sc and crc_degree is None:
+            raise ValueError("Hybrid SC requires an outer CRC.")
         self._n = n
         self._frozen_pos = frozen_pos
         self._k = self._n - len(self._frozen_pos)
@@ -122,12 +130,12 @@ class SCL_Dec(nn.Module):
         if (crc_degree is None) and return_crc_status:
             raise ValueError("Returning CRC status requires given crc_degree.")
         self._return_crc_status = return_crc_status
-        if use_hybrid_sc:
-            raise NotImplementedError("use_hybrid_sc: not implemented in the reference either (dec.py:497-498)")
         self._mask = mask
         check_supported(n, list_size)
         self._plans = _lib.PlanSet()
+        self._sc_plans = _lib.PlanSet()  # hybrid: the exact-f SC plan of the same code, per device
         self._pm = None
+        self.last_list_rows = 0
 
     @property
     def n(self):
@@ -172,18 +180,35 @@ class SCL_Dec(nn.Module):
             p.set_crc(*self._crc)
         return p
 
+    def sc_plan(self, device=None):
+        """The hybrid decoder's SC plan on `device`: exact f, the list plan's frozen set and llr_max."""
+        return self._sc_plans.get(device, self._make_sc_plan)
+
+    def _make_sc_plan(self, dev):
+        return _lib.Plan(self._n, self._mask, 1, _lib.PL_F_EXACT, self._llr_max, device=dev)
+
     def forward(self, inputs):
         assert inputs.dtype == self.output_dtype, "Invalid input dtype."
         inputs = inputs.to(tc.float32)
         assert inputs.shape[-1] == self._n, "Last input dimension must be of length n."
         assert inputs.dim() > 1
-        if self._return_crc_status:
-            raise NotImplementedError("return_crc_status: not implemented in the reference either (dec.py:534-535)")
         input_shape = inputs.shape
         llr = inputs.reshape([-1, self._n])
         dev = _gpu_for(llr, self.device)
-        u_hat, self._pm = ops.scl_decode(self.plan(dev), llr.to(dev, non_blocking=True), return_pm=True)
+        crc_ok = None
+        if self._use_hybrid_sc:
+            u_hat, crc_ok, _, self.last_list_rows = ops.hybrid_decode(
+                self.sc_plan(dev), self.plan(dev), llr.to(dev, non_blocking=True), return_info=True)
+            self._pm = None
+        else:
+            u_hat, self._pm = ops.scl_decode(self.plan(dev), llr.to(dev, non_blocking=True), return_pm=True)
+            self.last_list_rows = u_hat.shape[0]
+            if self._return_crc_status:
+                crc_ok = ops.crc_status(self.plan(dev), u_hat)
         output_shape = list(input_shape)
         output_shape[-1] = self.k
         output_shape[0] = -1
-        return u_hat.reshape(output_shape).to(self.output_dtype).to(device=self.device)
+        u_hat = u_hat.reshape(output_shape).to(self.output_dtype).to(device=self.device)
+        if not self._return_crc_status:
+            return u_hat
+        return u_hat, crc_ok.reshape(list(input_shape[:-1])).to(device=self.device)

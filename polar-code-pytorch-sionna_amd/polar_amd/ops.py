@@ -92,6 +92,76 @@ def scl_decode(plan, llr_logits, out=None, out_dtype=torch.float32, return_pm=Fa
     return (out, pm) if return_pm else out
 
 
+_hybrid_ws = {}  # (device, stream) -> the last hybrid workspace used there (grown, never shrunk)
+
+
+def hybrid_workspace(sc_plan, scl_plan, bs, device):
+    """A device workspace of pl_hybrid_workspace_size(sc_plan, scl_plan, bs) bytes, cached per
+    device and stream and by size: one call after another on a stream reuses it (stream order
+    keeps them apart), and a larger batch replaces it."""
+    ws_bytes = int(_lib.lib().pl_hybrid_workspace_size(sc_plan.handle, scl_plan.handle, bs))
+    device = torch.device(device)
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _hybrid_ws.get(key)
+    if ws is None or ws.numel() < ws_bytes:
+        ws = _hybrid_ws[key] = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def hybrid_decode(sc_plan, scl_plan, llr_logits, out=None, out_dtype=torch.float32, return_info=False):
+    """Hybrid SC / SC-list decode (pl_hybrid_decode) of [bs, n] fp32 logits -> [bs, k] bits:
+    sc_plan decodes every row, scl_plan (a list plan with a CRC, of the same code) decodes again
+    the rows whose SC result fails the CRC.  return_info: also (crc_ok bool [bs]: the CRC of the
+    row's output; list_rows int32 [n_list]: the rows that were list-decoded, ascending; n_list).
+    The call synchronises the current stream once (the count of failing rows is read back)."""
+    _require_cuda(llr_logits, "llr_logits")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != scl_plan.n:
+        raise ValueError(f"llr_logits must be [bs, {scl_plan.n}], got {tuple(x.shape)}")
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, scl_plan.k), dtype=out_dtype, device=x.device)
+    elif out.shape != (bs, scl_plan.k) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+    ok = torch.empty((bs,), dtype=torch.uint8, device=x.device) if return_info else None
+    rows = torch.empty((bs,), dtype=torch.int32, device=x.device) if return_info else None
+    n_list = ctypes.c_int64(0)
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        ws = hybrid_workspace(sc_plan, scl_plan, bs, x.device)
+        ws_bytes = int(L.pl_hybrid_workspace_size(sc_plan.handle, scl_plan.handle, bs))
+        _lib.check(L.pl_hybrid_decode(sc_plan.handle, scl_plan.handle, ctypes.c_void_p(x.data_ptr()), bs,
+                                      ctypes.c_void_p(out.data_ptr()), kind,
+                                      ctypes.c_void_p(ok.data_ptr() if return_info else 0),
+                                      ctypes.c_void_p(rows.data_ptr() if return_info else 0), ctypes.byref(n_list),
+                                      ctypes.c_void_p(ws.data_ptr()), ws_bytes, _lib.current_stream_ptr(x.device)),
+                   "pl_hybrid_decode")
+    if not return_info:
+        return out
+    return out, ok != 0, rows[: n_list.value], int(n_list.value)
+
+
+def crc_status(plan, bits):
+    """pl_crc_status: [bs, k] decoded bits (fp32 0/1 or uint8) -> bool [bs], True where the row
+    passes the CRC of the plan (pl_plan_set_crc; the last `degree` bits are the parity)."""
+    _require_cuda(bits, "bits")
+    b = bits
+    if b.dtype not in (torch.float32, torch.uint8):
+        b = b.to(torch.float32)
+    b = b.contiguous()
+    if b.dim() != 2 or b.shape[1] != plan.k:
+        raise ValueError(f"bits must be [bs, {plan.k}], got {tuple(b.shape)}")
+    valid = torch.empty((b.shape[0],), dtype=torch.uint8, device=b.device)
+    with torch.cuda.device(b.device):
+        _lib.check(_lib.lib().pl_crc_status(plan.handle, ctypes.c_void_p(b.data_ptr()), _out_kind(b.dtype), b.shape[0],
+                                            ctypes.c_void_p(valid.data_ptr()), _lib.current_stream_ptr(b.device)),
+                   "pl_crc_status")
+    return valid != 0
+
+
 def polar_encode(plan, u_bits, out=None):
     """Encode [bs, k] 0/1 fp32 information bits -> [bs, n] fp32 codewords (enc.py:30-43)."""
     _require_cuda(u_bits, "u_bits")

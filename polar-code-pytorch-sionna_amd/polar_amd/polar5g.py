@@ -384,9 +384,15 @@ class Polar5GEncoder(PolarEncoder):
 class Polar5GDecoder(nn.Module):
     """5G NR polar decoder: rate recovery + SC / CRC-aided SCL + CRC removal (dec.py:539-666)."""
 
-    def __init__(self, enc_polar, dec_type="SC", list_size=8, return_crc_status=False, output_dtype=tc.float32):
+    def __init__(self, enc_polar, dec_type="SC", list_size=8, return_crc_status=False, output_dtype=tc.float32,
+                 hybrid_sc=False):
+        """hybrid_sc (no reference counterpart; dec_type="hybSCL" cannot be constructed there or here):
+        with dec_type="SCL", the mother decoder is mysn.SCL_Dec(..., use_hybrid_sc=True) -- SC first,
+        the list decoder only on the rows whose CRC fails."""
         super().__init__()
         assert isinstance(enc_polar, Polar5GEncoder), "enc_polar must be a Polar5GEncoder."
+        if hybrid_sc and dec_type == "SC":
+            raise ValueError("hybrid_sc needs dec_type='SCL' (the SC decoder has no list stage).")
         self._output_dtype = output_dtype
         self._n_target, self._k_target = enc_polar.n_target, enc_polar.k_target
         self._n_polar, self._k_polar = enc_polar.n_polar, enc_polar.k_polar
@@ -402,7 +408,8 @@ class Polar5GDecoder(nn.Module):
             self._polar_dec = mysn.SC_Dec(enc_polar._frozen_pos, self._n_polar)
         elif dec_type == "SCL":
             self._polar_dec = mysn.SCL_Dec(enc_polar._frozen_pos, self._n_polar,
-                                           crc_degree=enc_polar.enc_crc.crc_degree, list_size=list_size)
+                                           crc_degree=enc_polar.enc_crc.crc_degree, list_size=list_size,
+                                           use_hybrid_sc=bool(hybrid_sc))
         elif dec_type == "hybSCL":
             raise NotImplementedError("hybSCL: the reference cannot construct it (dec.py:587-590)")
         else:
