@@ -244,6 +244,34 @@ int pl_sc_sim_count(const pl_plan* plan, uint64_t seed, uint64_t iteration, int6
                     int64_t* counts, void* workspace, size_t ws_bytes, float* llr_dump, float* u_dump,
                     void* hip_stream);
 
+/* The 5G NR link, fused (polar_amd.channel.FusedAWGN5G):
+ * pl_nr_awgn_qpsk_llr: for rows row0 .. row0+bs-1 of the keyed stream of pl_awgn_qpsk_llr, everything
+ *                  from the information bits to the mother decoder's input in one launch: BinarySource,
+ *                  Polar5GEncoder.forward (my_sn/fec/polar/enc.py:359-392), Gray QPSK, AWGN of variance
+ *                  no, the demapper, and rate recovery (Polar5GDecoder.forward, dec.py:609-638).
+ *                  plan: the mother code (32 <= n <= 1024, k = k_target + crc_degree).  The k_target
+ *                  information bits of a row are those pl_awgn_qpsk_llr draws for a code with k_target
+ *                  information bits (Philox domain 0).  g_rows / crc_degree: pl_crc_attach's tables and
+ *                  bit order.  Transmitted bit e < E is c[rm_idx[e]] of the mother codeword c (rm_idx:
+ *                  E entries, each < n); E even, 2 <= E <= 2176 (PL_EINVAL otherwise).  The noise of
+ *                  positions 4c .. 4c+3 is Philox block c of domain 1 of the row; logit = -2 sqrt(2) y / no.
+ *                  src_a / src_b (nullable) / fill (nullable): pl_rate_recover's tables (n entries,
+ *                  indices < E) and arithmetic, one fp32 add where two copies combine.
+ *                  Outputs (all nullable but llr_out): ubits_out [bs, ceil(k_target/32)] packed
+ *                  information bits (bits past k_target zero), u_out [bs, k_target] fp32 0/1,
+ *                  llr_ch_out [bs, E] fp32 channel logits (for tests), llr_out [bs, n] fp32 mother-code
+ *                  logits.  no > 0, 0 <= iteration < 2^32 as pl_awgn_qpsk_llr; bs == 0 is PL_OK.
+ * pl_count_errors_packed: bits [bs, row_len] decided bits of kind PL_OUT_F32 / PL_OUT_U8 (nonzero = 1)
+ *                  against ref_bits [bs, ceil(k_cmp/32)] packed as above: counts[0] += differing bits
+ *                  among the first k_cmp <= row_len columns of each row, counts[1] += rows with one
+ *                  (int64 device counters, accumulated, as pl_count_errors). */
+int pl_nr_awgn_qpsk_llr(const pl_plan* plan, int32_t k_target, const uint32_t* g_rows, int32_t crc_degree,
+                        const int32_t* rm_idx, int32_t e, const int32_t* src_a, const int32_t* src_b,
+                        const float* fill, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no,
+                        uint32_t* ubits_out, float* u_out, float* llr_ch_out, float* llr_out, void* hip_stream);
+int pl_count_errors_packed(const void* bits, int32_t kind, int64_t bs, int32_t row_len, int32_t k_cmp,
+                           const uint32_t* ref_bits, int64_t* counts, void* hip_stream);
+
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)
  * and ticks[2] (the chain's result) to the DEVICE buffer ticks[3]; clock GHz = 0.1 * ticks[0] /

@@ -207,7 +207,48 @@ class System_AWGN_model(nn.Module):
         return bits, bits_hat
 
 
-class FusedAWGN(nn.Module):
+class _KeyedDraws:
+    """The (SNR point, iteration) stream keys of the fused producers (FusedAWGN, FusedAWGN5G): see
+    FusedAWGN's docstring.  The model sets seed and row0 through _init_draws()."""
+
+    def _init_draws(self, seed, row0):
+        self.seed, self.row0, self.iteration = int(seed), int(row0), 0
+        self.epoch = 0  # runs of sim_ber over this model so far (next_epoch): part of the Philox key
+        if not 0 <= self.row0 < 2 ** 32:
+            raise ValueError(f"row0 must be in [0, 2^32), got {row0}")
+
+    def next_epoch(self):
+        """Start a new run: the following draws use a fresh Philox key (sim_ber calls this once
+        per run, so repeating a sweep over the same model does not repeat its codewords; the
+        reference draws them from its advancing global RNG)."""
+        self.epoch += 1
+
+    def key(self):
+        """The Philox key of the current epoch: the seed itself in epoch 0 (the pinned streams),
+        otherwise splitmix64(seed + epoch * golden gamma) -- a bijective mixer, so distinct epochs
+        of one seed get distinct keys, and related seeds (seed vs seed ^ gamma) do not replay each
+        other's epochs the way a plain seed ^ epoch * gamma key would."""
+        if self.epoch == 0:
+            return self.seed & (2 ** 64 - 1)
+        return splitmix64((self.seed + self.epoch * 0x9E3779B97F4A7C15) & (2 ** 64 - 1))
+
+    def _draw(self, batch_size, stream):
+        """(iteration, first stream row) of a draw of batch_size codewords."""
+        if stream is None:
+            point, it = 0, self.iteration
+            self.iteration += 1
+        else:
+            point, it = int(stream[0]), int(stream[1])
+        if not 0 <= it < 2 ** 32:
+            raise ValueError(f"Monte-Carlo iteration must be in [0, 2^32), got {it}")
+        if not 0 <= point < 2 ** 31:
+            raise ValueError(f"SNR point index must be in [0, 2^31), got {point}")
+        if self.row0 + int(batch_size) > 2 ** 32:
+            raise ValueError("row0 + batch_size must not exceed 2^32 (the point index is the row's high word)")
+        return it, self.row0 + (point << 32)
+
+
+class FusedAWGN(_KeyedDraws, nn.Module):
     """System_AWGN_model (awgn_model.py:17-44) with the whole producer -- bits, polar encoder, QPSK
     mapper, AWGN, demapper -- as one HIP kernel per call (pl_awgn_qpsk_llr).
 
@@ -235,48 +276,15 @@ class FusedAWGN(nn.Module):
         self.coderate = self.k / self.n
         self.decoder = decoder
         self.cw_estimates = cw_estimates
-        self.seed, self.row0, self.iteration = int(seed), int(row0), 0
-        self.epoch = 0  # runs of sim_ber over this model so far (next_epoch): part of the Philox key
-        if not 0 <= self.row0 < 2 ** 32:
-            raise ValueError(f"row0 must be in [0, 2^32), got {row0}")
+        self._init_draws(seed, row0)
         self._mask = frozen_mask(frozen_pos, self.n)
         assert self.n - int(self._mask.sum()) == self.k, "k must equal n - len(frozen_pos)"
         self.device = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
         self._plans = _lib.PlanSet()
 
-    def next_epoch(self):
-        """Start a new run: the following draws use a fresh Philox key (sim_ber calls this once
-        per run, so repeating a sweep over the same model does not repeat its codewords; the
-        reference draws them from its advancing global RNG)."""
-        self.epoch += 1
-
-    def key(self):
-        """The Philox key of the current epoch: the seed itself in epoch 0 (the pinned streams),
-        otherwise splitmix64(seed + epoch * golden gamma) -- a bijective mixer, so distinct epochs
-        of one seed get distinct keys, and related seeds (seed vs seed ^ gamma) do not replay each
-        other's epochs the way a plain seed ^ epoch * gamma key would."""
-        if self.epoch == 0:
-            return self.seed & (2 ** 64 - 1)
-        return splitmix64((self.seed + self.epoch * 0x9E3779B97F4A7C15) & (2 ** 64 - 1))
-
     def _make_plan(self, dev):
         from . import _lib
         return _lib.Plan(self.n, self._mask, 1, flags=_lib.PL_PLAN_GENERIC, device=dev)
-
-    def _draw(self, batch_size, stream):
-        """(iteration, first stream row) of a draw of batch_size codewords."""
-        if stream is None:
-            point, it = 0, self.iteration
-            self.iteration += 1
-        else:
-            point, it = int(stream[0]), int(stream[1])
-        if not 0 <= it < 2 ** 32:
-            raise ValueError(f"Monte-Carlo iteration must be in [0, 2^32), got {it}")
-        if not 0 <= point < 2 ** 31:
-            raise ValueError(f"SNR point index must be in [0, 2^31), got {point}")
-        if self.row0 + int(batch_size) > 2 ** 32:
-            raise ValueError("row0 + batch_size must not exceed 2^32 (the point index is the row's high word)")
-        return it, self.row0 + (point << 32)
 
     def llrs(self, batch_size, ebno_db, stream=None):
         from . import ops
@@ -326,6 +334,73 @@ class FusedAWGN(nn.Module):
         ubits, llr = ops.awgn_qpsk_llr_bits(self._plans.get(self.device, self._make_plan), int(batch_size), no,
                                             self.key(), it, row0)
         return ops.sc_decode_count(plan, llr, ubits, counts)
+
+
+class System5G_AWGN_model(System_AWGN_model):
+    """The 5G NR link from existing blocks, op by op: torch bits -> Polar5GEncoder.forward -> Mapper
+    -> AWGN -> Demapper -> Polar5GDecoder.forward, at the rate k_target / n_target (the unfused
+    comparator of FusedAWGN5G, as System_AWGN_model is of FusedAWGN)."""
+
+    def __init__(self, enc, dec, device='cpu', generator=None):
+        super().__init__(enc.n_target, enc.k_target, enc, dec, device=device, generator=generator)
+
+
+class FusedAWGN5G(_KeyedDraws, nn.Module):
+    """System5G_AWGN_model with everything up to the mother decoder's input -- information bits,
+    CRC attach, polar encoder, rate matching, QPSK mapper, AWGN, demapper, rate recovery -- as one HIP
+    kernel per call (pl_nr_awgn_qpsk_llr), and the error count on packed bits
+    (pl_count_errors_packed).
+
+    enc: an uplink Polar5GEncoder; dec: a Polar5GDecoder built on it (any dec_type / hybrid_sc).
+    The surface of FusedAWGN: forward(batch_size, ebno_db) -> (b, b_hat), both [bs, k_target];
+    error_counts(); keyed draws (stream=(point, iteration), next_epoch(), row0) with the same bounds
+    and errors; k = k_target.  no = ebnodb2no(ebno_db, 2, k_target / n_target)."""
+
+    keyed_streams = True  # sim_ber: draws depend on (point, iteration), not on call order
+
+    def __init__(self, enc, dec, device=None, seed=0, row0=0):
+        super().__init__()
+        from .polar5g import Polar5GDecoder, Polar5GEncoder
+        if not isinstance(enc, Polar5GEncoder) or not isinstance(dec, Polar5GDecoder):
+            raise ValueError("FusedAWGN5G needs a Polar5GEncoder and a Polar5GDecoder")
+        if enc._channel_type != "uplink":
+            raise ValueError("FusedAWGN5G: downlink is not supported (Polar5GEncoder.forward raises there too)")
+        if dec._enc_polar is not enc:
+            raise ValueError("FusedAWGN5G: dec must be the Polar5GDecoder built on enc")
+        self.encoder, self.decoder = enc, dec
+        self.n, self.k = enc.n_target, enc.k_target
+        self.n_bits_per_sym = 2
+        self.coderate = self.k / self.n
+        self._init_draws(seed, row0)
+        self.device = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
+
+    def _produce(self, batch_size, ebno_db, stream, **outputs):
+        from . import ops
+        no = float(ebnodb2no(float(ebno_db), self.n_bits_per_sym, self.coderate))
+        it, row0 = self._draw(batch_size, stream)
+        g_rows, rm_idx = self.encoder.tables(self.device)
+        src_a, src_b, fill = self.decoder.tables(self.device)
+        return ops.nr_awgn_qpsk_llr(self.encoder.plan(self.device), self.k, g_rows, self.encoder.crc_length, rm_idx,
+                                    src_a, src_b, fill, int(batch_size), no, self.key(), it, row0, **outputs)
+
+    def llrs(self, batch_size, ebno_db, stream=None):
+        """(bits [bs, k_target], None, mother-code logits [bs, n_polar])."""
+        bits, _, _, llr = self._produce(batch_size, ebno_db, stream, with_u=True, with_ubits=False)
+        return bits, None, llr
+
+    def forward(self, batch_size, ebno_db, stream=None):
+        bits, _, llr = self.llrs(batch_size, ebno_db, stream)
+        bits_hat = self.decoder.decode_mother(llr)[:, : self.k]
+        return bits, bits_hat.to(self.decoder._output_dtype)
+
+    def error_counts(self, batch_size, ebno_db, counts=None, stream=None):
+        """One Monte-Carlo iteration straight to the harness's counters: [bit errors, block errors]
+        (int64 [2] on the device, accumulated into counts) over the k_target information bits --
+        producer (packed bits, no fp32 bit rows), decode_mother, pl_count_errors_packed on the
+        k_polar-wide decoder output.  The same draw as forward() for this key."""
+        from . import ops
+        _, ubits, _, llr = self._produce(batch_size, ebno_db, stream, with_u=False, with_ubits=True)
+        return ops.count_errors_packed(self.decoder.decode_mother(llr), ubits, self.k, counts)
 
 
 def philox4x32_10(ctr, key):

@@ -3,6 +3,7 @@
     python -m polar_amd.cli --k 32 --n 64 --algos [scl] --bs 100 --mc_iter 1
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m polar_amd.cli \\
         --k 512 --n 1024 --bs 65536 --mc_iter 10 --snr_end 4.5
+    python -m polar_amd.cli --code 5g --k 500 --n 1024 --algos [scl] --hybrid_sc --bs 8192 --mc_iter 10
 
 Reference: main.py:32-76 (gen_code, seed 42 per code, SNR grid arange(0, snr_end, 0.5), SC always,
 SCL when 'scl' in algos, PlotBER.simulate with target_block_errs=1000) and config.py:5-26.
@@ -10,6 +11,10 @@ SCL when 'scl' in algos, PlotBER.simulate with target_block_errs=1000) and confi
 reference's RNG call order, decoded on the GPU); the default generates LLRs on the GPU.  With
 several ranks (torchrun, one per GPU) every rank simulates --bs codewords per iteration with its
 own RNG stream (seed 42 + rank) and the error counters are summed with one RCCL all_reduce.
+--code 5g simulates the rate-matched, CRC-aided 5G NR uplink code (Polar5GEncoder / Polar5GDecoder
+with --k, --n as k_target, n_target; no counterpart in main.py): the SC leg is dec_type="SC", the
+scl leg dec_type="SCL" with --list_size (and --hybrid_sc), the LLRs from the fused 5G producer
+(channel.FusedAWGN5G) or, with --llr_producer ops, from the op-by-op chain (System5G_AWGN_model).
 """
 import argparse
 import math
@@ -46,6 +51,11 @@ def parse(argv=None):
     ap.add_argument("--target_block_errs", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--plot", default=None, help="save the BLER plot here (matplotlib)")
+    ap.add_argument("--code", choices=["plain", "5g"], default="plain",
+                    help="plain: the (k, n) polar code of main.py; 5g: the 5G NR uplink code with --k, --n as "
+                         "k_target, n_target (CRC, rate matching)")
+    ap.add_argument("--hybrid_sc", action="store_true",
+                    help="--code 5g, scl leg: SC first, the list decoder only on rows whose CRC fails")
     ap.add_argument("--frozen", choices=["reference", "recompute"], default="reference",
                     help="reference: the pinned sets froze.py produced; recompute: re-run froze.py's recipe")
     return ap.parse_args(argv)
@@ -57,9 +67,32 @@ def set_seed(seed):  # main.py:24-29
     tc.manual_seed(seed)
 
 
+def gen_code_5g(c, name, mode, device, generator=None):
+    """[model, name] of the 5G NR uplink code (k_target, n_target) = (--k, --n) on a GPU."""
+    from . import channel
+    from .polar5g import Polar5GDecoder, Polar5GEncoder
+    if device.type != "cuda":
+        raise ValueError("--code 5g runs on the GPU (--llr_device cuda)")
+    enc = Polar5GEncoder(c.k, c.n)
+    if mode == "sc":
+        dec = Polar5GDecoder(enc, dec_type="SC")
+    elif mode == "scl":
+        dec = Polar5GDecoder(enc, dec_type="SCL", list_size=c.list_size, hybrid_sc=c.hybrid_sc)
+    else:
+        raise Exception('error...')
+    if c.llr_producer == "fused":
+        rank = int(os.environ.get("RANK", "0"))  # rank r draws stream rows [r*bs, (r+1)*bs)
+        model = channel.FusedAWGN5G(enc, dec, device=device, seed=c.seed, row0=rank * c.bs)
+    else:
+        model = channel.System5G_AWGN_model(enc, dec, device=device, generator=generator)
+    return [model, name]
+
+
 def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
     from . import channel, frozen
     from .decoders import SC_Dec, SCL_Dec
+    if getattr(c, "code", "plain") == "5g":
+        return gen_code_5g(c, name, mode, device, generator)
     assert math.log(c.n, 2).is_integer()
     G, _, fp = frozen.get_Kern_frozen_bits(c.n, c.n - c.k, frozen.F2)
     if c.frozen == "reference":

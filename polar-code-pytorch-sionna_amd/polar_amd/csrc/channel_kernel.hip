@@ -262,11 +262,266 @@ __global__ __launch_bounds__(256) void awgn_llr_kernel(int64_t bs, int64_t row0,
     }
 }
 
+// nr_awgn_llr_kernel: the 5G NR link up to the mother decoder's input, one launch -- BinarySource,
+// Polar5GEncoder.forward (my_sn/fec/polar/enc.py:359-392: CRC attach, polar encode, rate matching),
+// Gray QPSK, AWGN, the demapper, and Polar5GDecoder.forward's rate recovery (dec.py:609-638).
+// The wave layout is awgn_llr_kernel's (cpw = 64 / wpc rows per wave, wpc = n / 32 lanes per row,
+// n = n_polar = 32 ... 1024), with these phases:
+//   A   stream words of the kt = k_target information bits (the streams of awgn_llr_kernel) -> LDS;
+//   A'  CRC parity (pl_crc_attach's rule): each lane XORs the generator rows of the 1 bits of its
+//       word, an XOR reduction over the row's lanes; [information bits | parity] -> LDS;
+//   B   as awgn_llr_kernel, over the k = kt + degree bits: deposit, butterfly -> code words in LDS;
+//   C   in passes of R rows (R * 4 ceil(E/4) <= kNrStage floats of LDS per wave):
+//       C2  the wave's lanes over (row, chunk of 4 transmitted positions): bit e = c[rm_idx[e]],
+//           noise block `chunk` of domain 1 (one Philox block per 4 positions, as awgn_llr_kernel
+//           with E in place of n), logits -> the LDS stage (and llr_ch_out);
+//       C3  the wave's lanes over (row, 4 mother positions): pl_rate_recover's rule gathered from
+//           the stage (one fp32 add where two copies combine), whole-line stores to llr_out.
+// The generator rows sit in LDS once per block, padded by one word per 32 so that the lanes of a
+// row (word stride 32) read distinct banks.
+constexpr int kNrStage = 2176;              // stage floats per wave: two rows of E = 1088
+constexpr int kNrMaxK = 1024;               // generator rows staged per block
+constexpr int kNrGWords = kNrMaxK + kNrMaxK / 32;
+
+__global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
+    int64_t bs, int64_t row0, uint32_t k0, uint32_t k1, uint32_t it, float no, const uint32_t* __restrict__ frozen_words,
+    int n, int k, int kt, const uint32_t* __restrict__ g_rows, int degree, const int32_t* __restrict__ rm_idx, int e_len,
+    const int32_t* __restrict__ src_a, const int32_t* __restrict__ src_b, const float* __restrict__ fill,
+    float* __restrict__ u_out, uint32_t* __restrict__ ubits_out, float* __restrict__ llr_ch_out,
+    float* __restrict__ llr_out) {
+    __shared__ uint32_t s_g[kNrGWords];
+    __shared__ uint32_t lds[4 * 192];
+    __shared__ __attribute__((aligned(16))) float s_stage[4 * kNrStage];
+    const int wpc = n / 32, cpw = 64 / wpc;
+    const int nq = (kt + 31) / 32, nkq = (k + 31) / 32;  // words of the information bits / with the parity
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
+    uint32_t* sw = lds + wv * 192;                             // [cpw][nq] stream words
+    uint32_t* kw = sw + 64;                                    // [cpw][nkq] information bits | parity
+    uint32_t* cwd = sw + 128;                                  // [cpw][wpc] code words
+    float* st = s_stage + wv * kNrStage;
+    const int g = lane / wpc, w = lane % wpc;
+    const int64_t row = row0 + b0 + g;
+
+    for (int m = threadIdx.x; m < kt; m += 256) s_g[m + (m >> 5)] = g_rows[m];
+    // A: stream words (rows past bs compute harmless values that are never stored)
+    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
+    __syncthreads();
+
+    // A': parity of the row; nq <= wpc (kt < n), so lane w < nq owns word w of its row
+    const uint32_t last = (kt & 31) ? ((1u << (kt & 31)) - 1u) : 0xFFFFFFFFu;
+    const uint32_t mine = w < nq ? sw[g * nq + w] & (w == nq - 1 ? last : 0xFFFFFFFFu) : 0u;
+    uint32_t par = 0u;
+    {
+        const uint32_t* gr = s_g + w * 33;
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j)
+            if ((mine >> j) & 1u) par ^= gr[j];
+    }
+    for (int d = 1; d < wpc; d <<= 1) par ^= (uint32_t)__shfl_xor((int)par, d, 64);
+    if (degree < 32) par &= (1u << degree) - 1u;
+    if (w < nkq) {
+        const uint64_t pv = (uint64_t)par << (kt & 31);  // parity bit c = bit kt + c of the row
+        const int pw = kt >> 5;
+        kw[g * nkq + w] = mine | (w == pw ? (uint32_t)pv : 0u) | (w == pw + 1 ? (uint32_t)(pv >> 32) : 0u);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    // B: the k bits deposited at the information positions, XOR butterfly (awgn_llr_kernel's B)
+    const uint32_t info = ~frozen_words[w];
+    int base = 0;
+    {
+        int c = __popc(info), incl = c;
+        for (int d = 1; d < wpc; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (w >= d) incl += o;
+        }
+        base = incl - c;
+    }
+    uint32_t x = 0u;
+    if (info) {
+        const uint32_t* srow = kw + g * nkq;
+        const int q0 = base >> 5, sh = base & 31;
+        const uint32_t lo = q0 < nkq ? srow[q0] : 0u;
+        const uint32_t hi = q0 + 1 < nkq ? srow[q0 + 1] : 0u;
+        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
+    }
+    for (int h = 1; h < 32; h <<= 1) x ^= (x >> h) & span_mask(h);
+    for (int hw = 1; hw < wpc; hw <<= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
+        if ((w & hw) == 0) x ^= other;
+    }
+    cwd[g * wpc + w] = x;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
+    if (rows <= 0) return;
+    // C1: u rows (BinarySource output, float32 0/1)
+    if (u_out != nullptr && kt > 0) {
+        if ((kt & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
+            const int kq = kt >> 2;
+            for (int c = lane; c < rows * kq; c += 64) {
+                const int r = c / kq, p = (c - r * kq) * 4;
+                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
+                reinterpret_cast<float4*>(u_out + (b0 + r) * kt)[p >> 2] =
+                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
+            }
+        } else {
+            for (int c = lane; c < rows * kt; c += 64) {
+                const int r = c / kt, p = c - r * kt;
+                u_out[(b0 + r) * kt + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
+            }
+        }
+    }
+    // C1': the information bits packed (pl_count_errors_packed's reference), bits past kt cleared
+    if (ubits_out != nullptr)
+        for (int c = lane; c < rows * nq; c += 64) {
+            const int q = c % nq;
+            ubits_out[b0 * nq + c] = sw[c] & (q == nq - 1 ? last : 0xFFFFFFFFu);
+        }
+
+    const float scale = -2.8284271f / no;
+    const Logit lc{scale * 0.70710677f, scale * sqrtf(no) * 0.70710677f * 1.17741002f};  // sqrt(2 ln 2)
+    const int nch = (e_len + 3) >> 2, epad = nch * 4;  // chunks of 4 transmitted positions per row
+    const int rpp = kNrStage / epad < cpw ? kNrStage / epad : cpw;  // rows per pass (>= 1: E <= kNrStage)
+    const bool ch_vec = (e_len & 3) == 0 && ((reinterpret_cast<uintptr_t>(llr_ch_out) & 15) == 0) &&
+                        ((reinterpret_cast<uintptr_t>(rm_idx) & 15) == 0);
+    const bool tab_vec = ((reinterpret_cast<uintptr_t>(src_a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(src_b) & 15) == 0) &&
+                         ((reinterpret_cast<uintptr_t>(fill) & 15) == 0) && ((reinterpret_cast<uintptr_t>(llr_out) & 15) == 0);
+    const int nj = n >> 2, lnj = __builtin_ctz(nj);
+    for (int r0 = 0; r0 < rows; r0 += rpp) {
+        const int rc = rows - r0 < rpp ? rows - r0 : rpp;
+        // C2: rate matching, QPSK, AWGN, demapper -> stage (+ llr_ch_out)
+        for (int c = lane; c < rc * nch; c += 64) {
+            const int rl = c / nch, ch = c - rl * nch, r = r0 + rl, p = ch * 4;
+            int id[4];
+            if (ch_vec) {
+                const int4 v = reinterpret_cast<const int4*>(rm_idx)[ch];
+                id[0] = v.x, id[1] = v.y, id[2] = v.z, id[3] = v.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) id[i] = p + i < e_len ? rm_idx[p + i] : 0;
+            }
+            const uint32_t* cw = cwd + r * wpc;
+            uint32_t bits = 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int j = id[i] & (n - 1);  // a table entry outside the codeword cannot leave the row
+                bits |= ((cw[j >> 5] >> (j & 31)) & 1u) << i;
+            }
+            const U4 rnd = stream_block(k0, k1, row0 + b0 + r, it, 1, (uint32_t)ch);
+            const float4 l = logits4(rnd, bits, lc);
+            *reinterpret_cast<float4*>(st + rl * epad + p) = l;
+            if (llr_ch_out != nullptr) {
+                float* o = llr_ch_out + (b0 + r) * e_len + p;
+                if (ch_vec) {
+                    *reinterpret_cast<float4*>(o) = l;
+                } else {
+                    const float lv[4] = {l.x, l.y, l.z, l.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (p + i < e_len) o[i] = lv[i];
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // C3: rate recovery (pl_rate_recover's tables and arithmetic) from the stage
+        for (int c = lane; c < rc * nj; c += 64) {
+            const int rl = c >> lnj, jc = c & (nj - 1), r = r0 + rl;
+            int a[4], b[4];
+            float f[4];
+            if (tab_vec) {
+                const int4 va = reinterpret_cast<const int4*>(src_a)[jc];
+                a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
+                b[0] = b[1] = b[2] = b[3] = -1;
+                if (src_b != nullptr) {
+                    const int4 vb = reinterpret_cast<const int4*>(src_b)[jc];
+                    b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
+                }
+                f[0] = f[1] = f[2] = f[3] = 0.0f;
+                if (fill != nullptr) {
+                    const float4 vf = reinterpret_cast<const float4*>(fill)[jc];
+                    f[0] = vf.x, f[1] = vf.y, f[2] = vf.z, f[3] = vf.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a[i] = src_a[jc * 4 + i];
+                    b[i] = src_b ? src_b[jc * 4 + i] : -1;
+                    f[i] = fill ? fill[jc * 4 + i] : 0.0f;
+                }
+            }
+            const float* x4 = st + rl * epad;
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // entries past E - 1 are clamped: a bad table reads another position, never another row
+                const int ia = a[i] < e_len ? a[i] : e_len - 1, ib = b[i] < e_len ? b[i] : e_len - 1;
+                v[i] = f[i];
+                if (ia >= 0) v[i] = ib >= 0 ? x4[ia] + x4[ib] : x4[ia];  // llr_1 + llr_3 (dec.py:629-633)
+            }
+            float* o = llr_out + (b0 + r) * n + jc * 4;
+            if (tab_vec) {
+                *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = v[i];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+constexpr int kRowsPerWave = 8;  // rows a wave of the counting kernels takes
+
+// Bit and block errors of the first k_cmp columns of [rows, row_len] decided bits (fp32 0/1 or
+// bytes) against packed reference bits ([rows, ceil(k_cmp/32)] words, bit m % 32 of word m / 32):
+// the layout of count_errors_kernel, the reference 1/32 of its bytes and no slice copy.
+template <typename T>
+__global__ __launch_bounds__(256) void count_errors_packed_kernel(const T* __restrict__ bits, int64_t rows, int row_len,
+                                                                  int k_cmp, const uint32_t* __restrict__ ref,
+                                                                  unsigned long long* __restrict__ counts) {
+    __shared__ unsigned long long part[4][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * kRowsPerWave;
+    const int nq = (k_cmp + 31) / 32;
+    uint32_t bit_err = 0, blk_err = 0;
+    for (int r = 0; r < kRowsPerWave; ++r) {
+        const int64_t row = r0 + r;
+        uint32_t e = 0;
+        if (row < rows)
+            for (int i = lane; i < k_cmp; i += 64) {
+                const uint32_t want = (ref[row * nq + (i >> 5)] >> (i & 31)) & 1u;
+                e += (bits[row * row_len + i] != (T)0 ? 1u : 0u) ^ want;
+            }
+        bit_err += e;
+        blk_err += __builtin_amdgcn_ballot_w64(e != 0) != 0 ? 1u : 0u;
+    }
+    for (int off = 32; off >= 1; off >>= 1) bit_err += __shfl_xor(bit_err, off, 64);
+    if (lane == 0) {
+        part[wv][0] = bit_err;
+        part[wv][1] = blk_err;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long be = part[0][0] + part[1][0] + part[2][0] + part[3][0];
+        const unsigned long long ke = part[0][1] + part[1][1] + part[2][1] + part[3][1];
+        if (be) atomicAdd(&counts[0], be);
+        if (ke) atomicAdd(&counts[1], ke);
+    }
+}
+
 // Bit and block errors of a [rows, k] pair of 0/1 float tensors (exact comparisons, as
 // tc.not_equal): a wave takes kRowsPerWave rows (their loads issued together, 16-byte loads when
 // rows are 16-byte aligned), the block reduces in LDS, one pair of 64-bit atomics per block.
-constexpr int kRowsPerWave = 8;
-
 __global__ __launch_bounds__(256) void count_errors_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            int64_t rows, int k, unsigned long long* __restrict__ counts) {
     __shared__ unsigned long long part[4][2];
@@ -391,6 +646,71 @@ int pl_awgn_qpsk_llr_bits(const pl_plan* p, uint64_t seed, uint64_t iteration, i
                           uint32_t* ubits_out, float* llr_out, void* stream) {
     return awgn_launch(p, seed, iteration, row0, bs, no, nullptr, ubits_out, llr_out, stream,
                        "pl_awgn_qpsk_llr_bits");
+}
+
+int pl_nr_awgn_qpsk_llr(const pl_plan* p, int32_t k_target, const uint32_t* g_rows, int32_t crc_degree,
+                        const int32_t* rm_idx, int32_t e, const int32_t* src_a, const int32_t* src_b, const float* fill,
+                        uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no, uint32_t* ubits_out,
+                        float* u_out, float* llr_ch_out, float* llr_out, void* stream) {
+    const char* what = "pl_nr_awgn_qpsk_llr";
+    if (!p || bs < 0 || row0 < 0 || (bs > 0 && !llr_out) || !(no > 0.0f) || (iteration >> 32) != 0) {
+        pl::set_error(std::string(what) + ": bad arguments (no must be > 0, iteration < 2^32)");
+        return PL_EINVAL;
+    }
+    if (p->n < 32 || p->n > 1024) {
+        pl::set_error(std::string(what) + ": the mother code length must be 32 ... 1024");
+        return PL_EINVAL;
+    }
+    if (k_target < 0 || crc_degree < 1 || crc_degree > 32 || p->k != k_target + crc_degree) {
+        pl::set_error(std::string(what) + ": the plan's k must equal k_target + crc_degree (crc_degree 1 ... 32)");
+        return PL_EINVAL;
+    }
+    if (e < 2 || (e & 1) || e > kNrStage) {
+        pl::set_error(std::string(what) + ": E must be even (whole QPSK symbols), 2 ... " + std::to_string(kNrStage));
+        return PL_EINVAL;
+    }
+    if (bs > 0 && (!rm_idx || !src_a || (k_target > 0 && !g_rows))) {
+        pl::set_error(std::string(what) + ": g_rows, rm_idx and src_a must be given");
+        return PL_EINVAL;
+    }
+    if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
+    if (bs == 0) return PL_OK;
+    const int64_t cpw = 64 / (p->n / 32);
+    const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
+    if (blocks > 0x7fffffffLL) {
+        pl::set_error(std::string(what) + ": batch too large for one launch");
+        return PL_EINVAL;
+    }
+    hipLaunchKernelGGL(nr_awgn_llr_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs,
+                       row0, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n,
+                       p->k, k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, u_out, ubits_out, llr_ch_out,
+                       llr_out);
+    return pl::check_hip(hipGetLastError(), what);
+}
+
+int pl_count_errors_packed(const void* bits, int32_t kind, int64_t bs, int32_t row_len, int32_t k_cmp,
+                           const uint32_t* ref_bits, int64_t* counts, void* stream) {
+    if (bs < 0 || row_len < 0 || k_cmp < 0 || k_cmp > row_len || !counts || (kind != PL_OUT_F32 && kind != PL_OUT_U8) ||
+        (bs > 0 && k_cmp > 0 && (!bits || !ref_bits))) {
+        pl::set_error("pl_count_errors_packed: bad arguments (0 <= k_cmp <= row_len, kind PL_OUT_F32 / PL_OUT_U8)");
+        return PL_EINVAL;
+    }
+    if (bs == 0 || k_cmp == 0) return PL_OK;
+    const int64_t blocks = (bs + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave);
+    if (blocks > 0x7fffffffLL) {
+        pl::set_error("pl_count_errors_packed: too many rows for one launch");
+        return PL_EINVAL;
+    }
+    unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
+    if (kind == PL_OUT_F32)
+        hipLaunchKernelGGL(count_errors_packed_kernel<float>, dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const float*>(bits), bs, row_len, k_cmp,
+                           ref_bits, c);
+    else
+        hipLaunchKernelGGL(count_errors_packed_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const uint8_t*>(bits), bs, row_len, k_cmp,
+                           ref_bits, c);
+    return pl::check_hip(hipGetLastError(), "pl_count_errors_packed launch");
 }
 
 int pl_count_errors(const float* a, const float* b, int64_t rows, int32_t k, int64_t* counts, void* stream) {

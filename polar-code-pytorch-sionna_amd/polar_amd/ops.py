@@ -222,6 +222,88 @@ def awgn_qpsk_llr_bits(plan, bs, no, seed, iteration, row0=0):
     return ubits, llr
 
 
+def _table(t, dtype, numel, name, device, optional=False):
+    """A device table handed to a kernel as a raw pointer: contiguous, of this dtype, length and device."""
+    if t is None and optional:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel \
+            or t.device != torch.device(device):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of {numel} elements on {device}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on "
+                         f"{getattr(t, 'device', None)}")
+    return t
+
+
+def nr_awgn_qpsk_llr(plan, k_target, g_rows, crc_degree, rm_idx, src_a, src_b, fill, bs, no, seed, iteration, row0=0,
+                     with_u=True, with_ubits=True, with_ch=False):
+    """The fused 5G NR link producer (pl_nr_awgn_qpsk_llr) on the mother-code plan's device: for rows
+    row0.. of the (seed, iteration) stream, information bits -> CRC attach -> polar encode -> rate
+    matching -> QPSK -> AWGN of variance `no` -> demapper -> rate recovery, one launch.
+    g_rows int32 [k_target] and crc_degree (bits): Polar5GEncoder.tables()[0] / crc_length; rm_idx
+    int32 [E]: tables()[1]; src_a, src_b (or None), fill (or None): Polar5GDecoder.tables().
+    Returns (u [bs, k_target] fp32 or None, ubits [bs, ceil(k_target/32)] int32 or None,
+    llr_ch [bs, E] fp32 or None, llr [bs, n] fp32), the optional ones as with_u / with_ubits / with_ch
+    say.  Bad values (odd E, no <= 0, a plan whose k is not k_target + crc_degree, an iteration outside
+    [0, 2^32)) raise PolarArgumentError from the library."""
+    dev = plan.device
+    k_target, bs = int(k_target), int(bs)
+    if k_target < 0 or bs < 0:
+        raise ValueError(f"k_target and bs must be >= 0, got {k_target}, {bs}")
+    if not isinstance(rm_idx, torch.Tensor) or rm_idx.dim() != 1:
+        raise ValueError("rm_idx must be a 1-D int32 tensor (the rate-matching gather index)")
+    e = int(rm_idx.numel())
+    g_rows = _table(g_rows, torch.int32, k_target, "g_rows", dev)
+    rm_idx = _table(rm_idx, torch.int32, e, "rm_idx", dev)
+    src_a = _table(src_a, torch.int32, plan.n, "src_a", dev)
+    src_b = _table(src_b, torch.int32, plan.n, "src_b", dev, optional=True)
+    fill = _table(fill, torch.float32, plan.n, "fill", dev, optional=True)
+    nq = (k_target + 31) // 32
+    llr = torch.empty((bs, plan.n), dtype=torch.float32, device=dev)
+    u = torch.empty((bs, k_target), dtype=torch.float32, device=dev) if with_u else None
+    ubits = torch.empty((bs, nq), dtype=torch.int32, device=dev) if with_ubits else None
+    ch = torch.empty((bs, e), dtype=torch.float32, device=dev) if with_ch else None
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pl_nr_awgn_qpsk_llr(plan.handle, k_target, ptr(g_rows), int(crc_degree), ptr(rm_idx), e,
+                                                  ptr(src_a), ptr(src_b), ptr(fill), int(seed) & (2 ** 64 - 1),
+                                                  int(iteration) & (2 ** 64 - 1), int(row0), bs, float(no),
+                                                  ptr(ubits), ptr(u), ptr(ch), ptr(llr),
+                                                  _lib.current_stream_ptr(dev)), "pl_nr_awgn_qpsk_llr")
+    return u, ubits, ch, llr
+
+
+def count_errors_packed(bits, ref_bits, k_cmp=None, counts=None):
+    """pl_count_errors_packed: [bit errors, block errors] (int64, on the device) of the first k_cmp
+    columns (default: all) of `bits` ([bs, row_len] fp32 0/1 or uint8, e.g. a decoder's k_polar-wide
+    output) against `ref_bits` ([bs, ceil(k_cmp/32)] int32 words, nr_awgn_qpsk_llr's / pack_bits'
+    layout); accumulates into counts (created if None) and returns it."""
+    _require_cuda(bits, "bits")
+    b = bits
+    if b.dtype not in (torch.float32, torch.uint8):
+        b = b.to(torch.float32)
+    b = b.contiguous()
+    if b.dim() != 2:
+        raise ValueError(f"bits must be [bs, row_len], got {tuple(b.shape)}")
+    bs, row_len = b.shape
+    k_cmp = row_len if k_cmp is None else int(k_cmp)
+    if not 0 <= k_cmp <= row_len:
+        raise ValueError(f"k_cmp must be in [0, {row_len}], got {k_cmp}")
+    nq = (k_cmp + 31) // 32
+    if not isinstance(ref_bits, torch.Tensor) or ref_bits.shape != (bs, nq) or ref_bits.dtype != torch.int32 \
+            or ref_bits.device != b.device:
+        raise ValueError(f"ref_bits must be int32 [{bs}, {nq}] on the input's device")
+    ref = ref_bits.contiguous()
+    counts = _counts(counts, b.device)
+    with torch.cuda.device(b.device):
+        _lib.check(_lib.lib().pl_count_errors_packed(ctypes.c_void_p(b.data_ptr()), _out_kind(b.dtype), bs, row_len,
+                                                     k_cmp, ctypes.c_void_p(ref.data_ptr()),
+                                                     ctypes.c_void_p(counts.data_ptr()),
+                                                     _lib.current_stream_ptr(b.device)), "pl_count_errors_packed")
+    return counts
+
+
 def pack_bits(bits):
     """[..., k] 0/1 tensor -> [rows, ceil(k/32)] int32 words in pl_sc_decode_count's layout."""
     k = bits.shape[-1]

@@ -501,6 +501,16 @@ class Polar5GDecoder(nn.Module):
     def polar_dec(self):
         return self._polar_dec
 
+    def decode_mother(self, llr_dec):
+        """forward() without the rate recovery: [bs, n_polar] mother-code logits on the GPU (what
+        rate_recover returns, or pl_nr_awgn_qpsk_llr produces) -> the mother decoder's [bs, k_polar]
+        bits (information bits, then the CRC), fp32 on the input's device."""
+        ops._require_cuda(llr_dec, "llr_dec")
+        if llr_dec.dim() != 2 or llr_dec.shape[1] != self._n_polar:
+            raise ValueError(f"llr_dec must be [bs, {self._n_polar}], got {tuple(llr_dec.shape)}")
+        # the mother decoder returns on its own device (SCL_Dec: self.device, polar_scl.py:234)
+        return self._polar_dec(llr_dec.to(tc.float32)).to(llr_dec.device)
+
     def forward(self, inputs):
         inputs = inputs.to(tc.float32)
         input_shape = inputs.shape
@@ -508,8 +518,7 @@ class Polar5GDecoder(nn.Module):
         llr_ch = inputs.reshape([-1, self._n_target])
         dev = _gpu_for(llr_ch, getattr(self._enc_polar, "device", None))
         llr_dec = self.rate_recover(llr_ch.to(dev))
-        # the mother decoder returns on its own device (SCL_Dec: self.device, polar_scl.py:234)
-        u_hat_crc = self._polar_dec(llr_dec).to(dev)
+        u_hat_crc = self.decode_mother(llr_dec)
         u_hat = u_hat_crc[:, : self._k_target]
         output_shape = [*input_shape]
         output_shape[-1] = self._k_target
