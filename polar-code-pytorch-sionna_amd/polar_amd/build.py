@@ -276,6 +276,12 @@ def reference_codes():
         for code in range(1, 1 << n):
             m = np.array([((code >> i) & 1) ^ 1 for i in range(n)], dtype=np.uint8)
             out += [(m, 1), (m, 1 | 0x100)]
+    # tests/test_exactf_ulp_gpu.py: only position 1 information (its LLR is the sum of the f trees
+    # over the even and the odd inputs), exact f, both ranges
+    for n in (8, 64, 256, 1024):
+        m = np.ones(n, dtype=np.uint8)
+        m[1] = 0
+        out += [(m, 1), (m, 1 | 0x100)]
     uniq = {}
     for m, fm in out:
         uniq[(bytes(bytearray(m)), fm)] = (m, fm)
