@@ -272,6 +272,38 @@ int pl_nr_awgn_qpsk_llr(const pl_plan* plan, int32_t k_target, const uint32_t* g
 int pl_count_errors_packed(const void* bits, int32_t kind, int64_t bs, int32_t row_len, int32_t k_cmp,
                            const uint32_t* ref_bits, int64_t* counts, void* hip_stream);
 
+/* Square QAM for the two fused producers (polar_amd.channel.FusedAWGN / FusedAWGN5G, num_bits_per_symbol):
+ * pl_awgn_qam_llr: pl_awgn_qpsk_llr / pl_awgn_qpsk_llr_bits with 2^m-QAM, m = bits_per_symbol in {2, 4, 6, 8}.
+ *                  Symbol s of a row carries code positions m s .. m s + m - 1, the first bit the most
+ *                  significant of the label (Mapper, my_sn/trans/mapping.py:135-148); the real part is the
+ *                  Gray PAM level of bits b[0::2], the imaginary part that of b[1::2], unit energy
+ *                  (mapping.py:7-48).  Noise: Philox domain 1, block c of the row serves symbols 2c (components
+ *                  x, y: re, im) and 2c + 1 (z, w).  Logits log P(b=1)/P(b=0) by the reference's formula
+ *                  (mapping.py:225-241, :195-205), evaluated per axis (for Gray square QAM the sum over the
+ *                  2^m points factors), max-subtracted, fp32 with the library exp / log.
+ *                  m must divide the plan's n (so m = 6 is refused for every plain power-of-two code).
+ *                  u_out [bs, k] fp32 and ubits_out [bs, ceil(k/32)] packed (both nullable; the layouts of
+ *                  pl_awgn_qpsk_llr / _bits), y_out (nullable, for tests) [bs, n/m, 2] fp32 received symbols
+ *                  (re, im), llr_out [bs, n] fp32.  The information bits are those of pl_awgn_qpsk_llr for the
+ *                  same key: the modulation does not change which codeword is drawn.
+ *                  m == 2 launches the QPSK kernel with the same arguments (bit-identical to pl_awgn_qpsk_llr
+ *                  and pl_awgn_qpsk_llr_bits); y_out must be NULL there.
+ *                  PL_EINVAL (the message names the argument): bits_per_symbol not in {2, 4, 6, 8}, y_out with
+ *                  m == 2, n % m != 0, no <= 0, iteration >= 2^32, negative bs / row0, no llr_out.  bs == 0 is PL_OK.
+ * pl_nr_awgn_qam_llr: pl_nr_awgn_qpsk_llr with 2^m-QAM as above on the E transmitted positions (symbol s =
+ *                  positions m s .. m s + m - 1 after rate matching), plus y_out (nullable) [bs, E/m, 2].  E must
+ *                  be a multiple of m, m <= E <= 2176 (an odd symbol count leaves the second half of the last
+ *                  noise block unused).  llr_out is pl_rate_recover of llr_ch_out, bit for bit.  Every other
+ *                  argument, check and output as pl_nr_awgn_qpsk_llr; m == 2 calls it (y_out NULL). */
+int pl_awgn_qam_llr(const pl_plan* plan, int32_t bits_per_symbol, uint64_t seed, uint64_t iteration, int64_t row0,
+                    int64_t bs, float no, float* u_out, uint32_t* ubits_out, float* y_out, float* llr_out,
+                    void* hip_stream);
+int pl_nr_awgn_qam_llr(const pl_plan* plan, int32_t bits_per_symbol, int32_t k_target, const uint32_t* g_rows,
+                       int32_t crc_degree, const int32_t* rm_idx, int32_t e, const int32_t* src_a, const int32_t* src_b,
+                       const float* fill, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no,
+                       uint32_t* ubits_out, float* u_out, float* y_out, float* llr_ch_out, float* llr_out,
+                       void* hip_stream);
+
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)
  * and ticks[2] (the chain's result) to the DEVICE buffer ticks[3]; clock GHz = 0.1 * ticks[0] /

@@ -64,6 +64,9 @@ def _declare(L):
     L.pl_nr_awgn_qpsk_llr.argtypes = [P, i32, P, i32, P, i32, P, P, P, ctypes.c_uint64, ctypes.c_uint64, i64, i64,
                                       ctypes.c_float, P, P, P, P, P]
     L.pl_count_errors_packed.argtypes = [P, i32, i64, i32, i32, P, P, P]
+    L.pl_awgn_qam_llr.argtypes = [P, i32, ctypes.c_uint64, ctypes.c_uint64, i64, i64, ctypes.c_float, P, P, P, P, P]
+    L.pl_nr_awgn_qam_llr.argtypes = [P, i32, i32, P, i32, P, i32, P, P, P, ctypes.c_uint64, ctypes.c_uint64, i64, i64,
+                                     ctypes.c_float, P, P, P, P, P, P]
     L.pl_clock_probe.argtypes = [P, i32, P]
     L.pl_hybrid_workspace_size.argtypes = [P, P, i64]
     L.pl_hybrid_workspace_size.restype = ctypes.c_size_t
@@ -76,7 +79,8 @@ def _declare(L):
               L.pl_crc_attach, L.pl_crc_check,
               L.pl_gather_rows, L.pl_rate_recover, L.pl_awgn_qpsk_llr, L.pl_count_errors,
               L.pl_awgn_qpsk_llr_bits, L.pl_sc_decode_count, L.pl_sc_sim_count, L.pl_clock_probe,
-              L.pl_hybrid_decode, L.pl_crc_status, L.pl_nr_awgn_qpsk_llr, L.pl_count_errors_packed):
+              L.pl_hybrid_decode, L.pl_crc_status, L.pl_nr_awgn_qpsk_llr, L.pl_count_errors_packed,
+              L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr):
         f.restype = ctypes.c_int
     return L
 
@@ -114,7 +118,7 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_rate_recover", "pl_awgn_qpsk_llr", "pl_count_errors", "pl_awgn_qpsk_llr_bits",
                     "pl_sc_count_workspace_size", "pl_sc_decode_count", "pl_sc_sim_count", "pl_clock_probe",
                     "pl_hybrid_workspace_size", "pl_hybrid_decode", "pl_crc_status",
-                    "pl_nr_awgn_qpsk_llr", "pl_count_errors_packed",
+                    "pl_nr_awgn_qpsk_llr", "pl_count_errors_packed", "pl_awgn_qam_llr", "pl_nr_awgn_qam_llr",
                     "pl_last_error_string", "pl_version")
 
 

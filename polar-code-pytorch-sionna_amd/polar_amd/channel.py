@@ -175,12 +175,16 @@ class GpuEncoder(nn.Module):
 
 
 class System_AWGN_model(nn.Module):
-    """bits -> encoder -> QPSK -> AWGN -> demapper -> decoder (awgn_model.py:17-44)."""
+    """bits -> encoder -> QAM mapper -> AWGN -> demapper -> decoder (awgn_model.py:17-44; the
+    reference fixes QPSK there, its blocks take any square QAM: num_bits_per_symbol 2, 4, 6, 8
+    dividing n)."""
 
-    def __init__(self, n, k, encoder, decoder, cw_estimates=False, device='cpu', generator=None):
+    def __init__(self, n, k, encoder, decoder, cw_estimates=False, device='cpu', generator=None,
+                 num_bits_per_symbol=2):
         super().__init__()
+        from .ops import check_bits_per_symbol
         self.cw_estimates = cw_estimates
-        self.n_bits_per_sym = 2
+        self.n_bits_per_sym = check_bits_per_symbol(num_bits_per_symbol, n, "the code length n")
         self.n, self.k = n, k
         self.coderate = self.k / self.n
         self.constell = QamConstellation(self.n_bits_per_sym, device=device)
@@ -249,8 +253,9 @@ class _KeyedDraws:
 
 
 class FusedAWGN(_KeyedDraws, nn.Module):
-    """System_AWGN_model (awgn_model.py:17-44) with the whole producer -- bits, polar encoder, QPSK
-    mapper, AWGN, demapper -- as one HIP kernel per call (pl_awgn_qpsk_llr).
+    """System_AWGN_model (awgn_model.py:17-44) with the whole producer -- bits, polar encoder, QAM
+    mapper, AWGN, demapper -- as one HIP kernel per call (pl_awgn_qpsk_llr; pl_awgn_qam_llr for
+    num_bits_per_symbol = 4 or 8, which must divide n -- ValueError otherwise, 6 always).
 
     Same interface: forward(batch_size, ebno_db) -> (bits, bits_hat) (or (codewords, bits_hat)
     with cw_estimates), llrs(batch_size, ebno_db) -> (bits, None, logits).  Randomness is Philox
@@ -266,13 +271,14 @@ class FusedAWGN(_KeyedDraws, nn.Module):
     keyed_streams = True  # sim_ber: draws depend on (point, iteration), not on call order
 
     def __init__(self, n, k, frozen_pos, decoder, device=None, seed=42, row0=0, cw_estimates=False,
-                 sim_kernel=True):
+                 sim_kernel=True, num_bits_per_symbol=2):
         super().__init__()
         self.sim_kernel = bool(sim_kernel)  # error_counts: the fused producer+decoder kernel when the plan has it
         from . import _lib
         from .frozen import frozen_mask
+        from .ops import check_bits_per_symbol
         self.n, self.k = int(n), int(k)
-        self.n_bits_per_sym = 2
+        self.n_bits_per_sym = check_bits_per_symbol(num_bits_per_symbol, self.n, "the code length n")
         self.coderate = self.k / self.n
         self.decoder = decoder
         self.cw_estimates = cw_estimates
@@ -290,8 +296,11 @@ class FusedAWGN(_KeyedDraws, nn.Module):
         from . import ops
         no = float(ebnodb2no(float(ebno_db), self.n_bits_per_sym, self.coderate))
         it, row0 = self._draw(batch_size, stream)
-        bits, llr = ops.awgn_qpsk_llr(self._plans.get(self.device, self._make_plan), int(batch_size), no,
-                                      self.key(), it, row0)
+        plan = self._plans.get(self.device, self._make_plan)
+        if self.n_bits_per_sym == 2:
+            bits, llr = ops.awgn_qpsk_llr(plan, int(batch_size), no, self.key(), it, row0)
+        else:
+            bits, _, _, llr = ops.awgn_qam_llr(plan, self.n_bits_per_sym, int(batch_size), no, self.key(), it, row0)
         return bits, None, llr
 
     def forward(self, batch_size, ebno_db, stream=None):
@@ -309,7 +318,8 @@ class FusedAWGN(_KeyedDraws, nn.Module):
           * pl_sc_sim_count (sim_kernel=True and a specialised plan with 64 channel slots per
             lane): the whole iteration inside the SC kernel, nothing written to HBM but the
             counters; its Philox streams are its own (the same model, not forward()'s draw).
-          * otherwise pl_awgn_qpsk_llr_bits + pl_sc_decode_count: the producer writes the logits
+          * otherwise (always with num_bits_per_symbol != 2: the in-kernel iteration is QPSK-only)
+            pl_awgn_qpsk_llr_bits / pl_awgn_qam_llr + pl_sc_decode_count: the producer writes the logits
             and the information bits packed, the decoder compares its decisions with them -- the
             same draw as forward() for this iteration.
         Returns None (nothing drawn) when the decoder is not this package's SC_Dec on a specialised
@@ -324,6 +334,11 @@ class FusedAWGN(_KeyedDraws, nn.Module):
             return None
         no = float(ebnodb2no(float(ebno_db), self.n_bits_per_sym, self.coderate))
         it, row0 = self._draw(batch_size, stream)
+        if self.n_bits_per_sym != 2:  # the in-kernel iteration is QPSK-only: producer (packed bits) + decode_count
+            _, ubits, _, llr = ops.awgn_qam_llr(self._plans.get(self.device, self._make_plan), self.n_bits_per_sym,
+                                                int(batch_size), no, self.key(), it, row0, with_u=False,
+                                                with_ubits=True)
+            return ops.sc_decode_count(plan, llr, ubits, counts)
         if self.sim_kernel:
             try:
                 return ops.sc_sim_count(plan, int(batch_size), no, self.key(), it, row0, counts)
@@ -341,8 +356,9 @@ class System5G_AWGN_model(System_AWGN_model):
     -> AWGN -> Demapper -> Polar5GDecoder.forward, at the rate k_target / n_target (the unfused
     comparator of FusedAWGN5G, as System_AWGN_model is of FusedAWGN)."""
 
-    def __init__(self, enc, dec, device='cpu', generator=None):
-        super().__init__(enc.n_target, enc.k_target, enc, dec, device=device, generator=generator)
+    def __init__(self, enc, dec, device='cpu', generator=None, num_bits_per_symbol=2):
+        super().__init__(enc.n_target, enc.k_target, enc, dec, device=device, generator=generator,
+                         num_bits_per_symbol=num_bits_per_symbol)
 
 
 class FusedAWGN5G(_KeyedDraws, nn.Module):
@@ -354,12 +370,14 @@ class FusedAWGN5G(_KeyedDraws, nn.Module):
     enc: an uplink Polar5GEncoder; dec: a Polar5GDecoder built on it (any dec_type / hybrid_sc).
     The surface of FusedAWGN: forward(batch_size, ebno_db) -> (b, b_hat), both [bs, k_target];
     error_counts(); keyed draws (stream=(point, iteration), next_epoch(), row0) with the same bounds
-    and errors; k = k_target.  no = ebnodb2no(ebno_db, 2, k_target / n_target)."""
+    and errors; k = k_target.  no = ebnodb2no(ebno_db, num_bits_per_symbol, k_target / n_target);
+    num_bits_per_symbol = 4, 6, 8 (pl_nr_awgn_qam_llr) must divide n_target = E (ValueError otherwise)."""
 
     keyed_streams = True  # sim_ber: draws depend on (point, iteration), not on call order
 
-    def __init__(self, enc, dec, device=None, seed=0, row0=0):
+    def __init__(self, enc, dec, device=None, seed=0, row0=0, num_bits_per_symbol=2):
         super().__init__()
+        from .ops import check_bits_per_symbol
         from .polar5g import Polar5GDecoder, Polar5GEncoder
         if not isinstance(enc, Polar5GEncoder) or not isinstance(dec, Polar5GDecoder):
             raise ValueError("FusedAWGN5G needs a Polar5GEncoder and a Polar5GDecoder")
@@ -369,7 +387,7 @@ class FusedAWGN5G(_KeyedDraws, nn.Module):
             raise ValueError("FusedAWGN5G: dec must be the Polar5GDecoder built on enc")
         self.encoder, self.decoder = enc, dec
         self.n, self.k = enc.n_target, enc.k_target
-        self.n_bits_per_sym = 2
+        self.n_bits_per_sym = check_bits_per_symbol(num_bits_per_symbol, self.n, "the transmitted length E")
         self.coderate = self.k / self.n
         self._init_draws(seed, row0)
         self.device = tc.device(device) if device is not None else tc.device("cuda", tc.cuda.current_device())
@@ -380,8 +398,13 @@ class FusedAWGN5G(_KeyedDraws, nn.Module):
         it, row0 = self._draw(batch_size, stream)
         g_rows, rm_idx = self.encoder.tables(self.device)
         src_a, src_b, fill = self.decoder.tables(self.device)
-        return ops.nr_awgn_qpsk_llr(self.encoder.plan(self.device), self.k, g_rows, self.encoder.crc_length, rm_idx,
-                                    src_a, src_b, fill, int(batch_size), no, self.key(), it, row0, **outputs)
+        if self.n_bits_per_sym == 2:
+            return ops.nr_awgn_qpsk_llr(self.encoder.plan(self.device), self.k, g_rows, self.encoder.crc_length, rm_idx,
+                                        src_a, src_b, fill, int(batch_size), no, self.key(), it, row0, **outputs)
+        u, ubits, ch, _, llr = ops.nr_awgn_qam_llr(self.encoder.plan(self.device), self.n_bits_per_sym, self.k, g_rows,
+                                                   self.encoder.crc_length, rm_idx, src_a, src_b, fill, int(batch_size),
+                                                   no, self.key(), it, row0, **outputs)
+        return u, ubits, ch, llr
 
     def llrs(self, batch_size, ebno_db, stream=None):
         """(bits [bs, k_target], None, mother-code logits [bs, n_polar])."""

@@ -15,6 +15,7 @@ own RNG stream (seed 42 + rank) and the error counters are summed with one RCCL 
 with --k, --n as k_target, n_target; no counterpart in main.py): the SC leg is dec_type="SC", the
 scl leg dec_type="SCL" with --list_size (and --hybrid_sc), the LLRs from the fused 5G producer
 (channel.FusedAWGN5G) or, with --llr_producer ops, from the op-by-op chain (System5G_AWGN_model).
+--num_bits_per_symbol 4 / 6 / 8 runs either code over 16-, 64- or 256-QAM (main.py fixes QPSK).
 """
 import argparse
 import math
@@ -48,6 +49,8 @@ def parse(argv=None):
     ap.add_argument("--llr_device", choices=["cuda", "cpu"], default="cuda")
     ap.add_argument("--llr_producer", choices=["fused", "ops"], default="fused",
                     help="cuda LLRs: one fused HIP kernel (Philox; default) or the op-by-op torch port")
+    ap.add_argument("--num_bits_per_symbol", type=int, choices=[2, 4, 6, 8], default=2,
+                    help="modulation: QPSK (default; main.py's), 16-, 64- or 256-QAM; must divide --n")
     ap.add_argument("--target_block_errs", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--plot", default=None, help="save the BLER plot here (matplotlib)")
@@ -74,6 +77,7 @@ def gen_code_5g(c, name, mode, device, generator=None):
     if device.type != "cuda":
         raise ValueError("--code 5g runs on the GPU (--llr_device cuda)")
     enc = Polar5GEncoder(c.k, c.n)
+    m = getattr(c, "num_bits_per_symbol", 2)
     if mode == "sc":
         dec = Polar5GDecoder(enc, dec_type="SC")
     elif mode == "scl":
@@ -82,9 +86,9 @@ def gen_code_5g(c, name, mode, device, generator=None):
         raise Exception('error...')
     if c.llr_producer == "fused":
         rank = int(os.environ.get("RANK", "0"))  # rank r draws stream rows [r*bs, (r+1)*bs)
-        model = channel.FusedAWGN5G(enc, dec, device=device, seed=c.seed, row0=rank * c.bs)
+        model = channel.FusedAWGN5G(enc, dec, device=device, seed=c.seed, row0=rank * c.bs, num_bits_per_symbol=m)
     else:
-        model = channel.System5G_AWGN_model(enc, dec, device=device, generator=generator)
+        model = channel.System5G_AWGN_model(enc, dec, device=device, generator=generator, num_bits_per_symbol=m)
     return [model, name]
 
 
@@ -115,9 +119,11 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
         # one HIP launch for bits/encoder/mapper/channel/demapper; rank r draws stream rows
         # [r*bs, (r+1)*bs) of the seed's stream
         rank = int(os.environ.get("RANK", "0"))
-        model = channel.FusedAWGN(c.n, c.k, fp, dec, device=device, seed=c.seed, row0=rank * c.bs)
+        model = channel.FusedAWGN(c.n, c.k, fp, dec, device=device, seed=c.seed, row0=rank * c.bs,
+                                  num_bits_per_symbol=getattr(c, "num_bits_per_symbol", 2))
     else:
-        model = channel.System_AWGN_model(c.n, c.k, enc, dec, device=device, generator=generator)
+        model = channel.System_AWGN_model(c.n, c.k, enc, dec, device=device, generator=generator,
+                                          num_bits_per_symbol=getattr(c, "num_bits_per_symbol", 2))
     return [model, name]
 
 

@@ -480,6 +480,437 @@ __global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
     }
 }
 
+// ---- 16/64/256-QAM (M = bits per symbol = 4, 6, 8; H = M / 2 bits per axis) -------------------
+// Symbol s of a row carries positions M s .. M s + M - 1, first bit most significant (Mapper,
+// my_sn/trans/mapping.py:135-148); its real part is the Gray PAM level of bits b[0::2], its
+// imaginary part that of b[1::2] (mapping.py:7-48).  The 2^H unit-energy levels come from the host
+// (pl::qam_levels), indexed by the axis label (first bit = MSB).
+// Work item: one lane = one Philox noise block (domain 1, block c) = the symbol pair (2c, 2c + 1) =
+// 2M consecutive positions; components x, y are the Box-Muller pair of symbol 2c (re, im), z, w that
+// of symbol 2c + 1 -- logits4's radius/angle construction, and for M = 2 the QPSK layout above.
+struct Qam {
+    float lev[16];  // PAM level of axis label a < 2^H
+    float d;        // half the level spacing: the levels are the odd multiples of d
+    float inv2d;    // 1 / (2 d)
+};
+
+// The received pair (re0, im0, re1, im1) from the pair's noise block and its 2M code bits (position
+// i of the pair = bit i of `bits`); s_lev: the level table in LDS (the label is masked to 2^H - 1).
+template <int M>
+__device__ __forceinline__ float4 qam_receive(const U4& rnd, uint32_t bits, const float* s_lev, float rsig) {
+    constexpr int H = M / 2;
+    float x[4];
+#pragma unroll
+    for (int ax = 0; ax < 4; ++ax) {  // axis ax & 1 (0 re, 1 im) of symbol ax >> 1
+        uint32_t a = 0u;
+#pragma unroll
+        for (int j = 0; j < H; ++j) a |= ((bits >> ((ax >> 1) * M + 2 * j + (ax & 1))) & 1u) << (H - 1 - j);
+        x[ax] = s_lev[a & ((1u << H) - 1u)];
+    }
+    const float rs0 = rsig * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.x | 1u)));
+    const float rs1 = rsig * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.z | 1u)));
+    const float t0 = __uint_as_float(0x3F800000u | (rnd.y >> 9)), t1 = __uint_as_float(0x3F800000u | (rnd.w >> 9));
+    return float4{__builtin_fmaf(rs0, __builtin_amdgcn_cosf(t0), x[0]), __builtin_fmaf(rs0, __builtin_amdgcn_sinf(t0), x[1]),
+                  __builtin_fmaf(rs1, __builtin_amdgcn_cosf(t1), x[2]), __builtin_fmaf(rs1, __builtin_amdgcn_sinf(t1), x[3])};
+}
+
+// Logits of the H bits of one axis from its received component y, written to out[0], out[2], ...
+// (the symbol's bits alternate re, im).  lev: the 2^H levels (the kernel argument itself, scalar
+// registers, in the plain kernel; the LDS copy in the NR kernel, which has no scalar registers to
+// spare), d / inv2d: Qam's.  The reference's logsumexp over the 2^M points
+// (mapping.py:225-241, :195-205) factors per axis for a Gray square constellation: |y - c|^2 =
+// (y_re - l_re)^2 + (y_im - l_im)^2, and both sets of a real-axis bit hold every imaginary level,
+// so that factor cancels in the ratio.  Exponents are taken relative to l*, the level nearest y:
+//   t_l = (-(y - l)^2 + (y - l*)^2) / no = (l - l*) (2 y - l - l*) / no  <= 0,
+// the difference formed before the division (no y^2 term to cancel).  One exp per level serves all
+// H bits; where a set's sum comes near the fp32 underflow (small no: the set without l* lies far
+// from y) the lane repeats the sums with each set's own maximum, as torch.logsumexp does.
+// expf / logf are the library functions (a decoder input, not a noise draw).
+template <int H>
+__device__ __forceinline__ void qam_axis_llr(float y, const float* lev, float d, float inv2d, float inv_no, float* out) {
+    constexpr int NL = 1 << H;
+    float j = __builtin_rintf(__builtin_fmaf(y, inv2d, -0.5f));
+    j = fminf(fmaxf(j, -(float)(NL / 2)), (float)(NL / 2 - 1));
+    const float ls = __builtin_fmaf(2.0f, j, 1.0f) * d;
+    const float s = 2.0f * y - ls;
+    float t[NL], s0[H], s1[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) s0[i] = s1[i] = 0.0f;
+#pragma unroll
+    for (int a = 0; a < NL; ++a) {
+        const float l = lev[a];
+        t[a] = (l - ls) * (s - l) * inv_no;
+        const float w = expf(t[a]);
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            if ((a >> (H - 1 - i)) & 1) s1[i] += w;
+            else s0[i] += w;
+        }
+    }
+    float low = s0[0];
+#pragma unroll
+    for (int i = 0; i < H; ++i) low = fminf(low, fminf(s0[i], s1[i]));
+    if (low >= 1e-30f) {
+#pragma unroll
+        for (int i = 0; i < H; ++i) out[2 * i] = logf(s1[i]) - logf(s0[i]);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        float m0 = -INFINITY, m1 = -INFINITY;
+#pragma unroll
+        for (int a = 0; a < NL; ++a) {
+            if ((a >> (H - 1 - i)) & 1) m1 = fmaxf(m1, t[a]);
+            else m0 = fmaxf(m0, t[a]);
+        }
+        float z0 = 0.0f, z1 = 0.0f;
+#pragma unroll
+        for (int a = 0; a < NL; ++a) {
+            if ((a >> (H - 1 - i)) & 1) z1 += expf(t[a] - m1);
+            else z0 += expf(t[a] - m0);
+        }
+        out[2 * i] = (m1 - m0) + (logf(z1) - logf(z0));
+    }
+}
+
+// awgn_qam_llr_kernel<M>: awgn_llr_kernel with a 2^M-QAM mapper and demapper (M = 4, 8; M divides n).
+// Phases A, B, C1, C1' are awgn_llr_kernel's; C2 takes the wave's lanes over (row, symbol pair).
+// y_out (nullable): [bs, n / M, 2] fp32 received symbols (re, im).
+template <int M>
+__global__ __launch_bounds__(256) void awgn_qam_llr_kernel(int64_t bs, int64_t row0, uint32_t k0, uint32_t k1, uint32_t it,
+                                                           float no, const uint32_t* __restrict__ frozen_words, int n,
+                                                           int k, Qam qam, float* __restrict__ u_out,
+                                                           float* __restrict__ llr_out, uint32_t* __restrict__ ubits_out,
+                                                           float* __restrict__ y_out) {
+    __shared__ uint32_t lds[4 * kWordsPerWave];
+    __shared__ float s_lev[16];
+    const int wpc = n >= 32 ? n / 32 : 1, cpw = 64 / wpc, nb = n >= 32 ? 32 : n;
+    const int nq = (k + 31) / 32;  // stream words per row
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
+    uint32_t* sw = lds + wv * kWordsPerWave;                   // [cpw][nq] stream words
+    uint32_t* cwd = sw + cpw * nq;                             // [cpw][wpc] code words
+    const int g = lane / wpc, w = lane % wpc;
+    const int64_t row = row0 + b0 + g;
+
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int a = 0; a < 16; ++a) s_lev[a] = qam.lev[a];
+    }
+    // A: stream words (rows past bs compute harmless values that are never stored)
+    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
+    __syncthreads();
+
+    // B: information positions of this word (frozen bit 0), their first rank = information
+    // positions in the group's earlier words (prefix sum over the group's lanes)
+    const uint32_t live = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+    const uint32_t info = ~frozen_words[w] & live;
+    int base = 0;
+    {
+        int c = __popc(info), incl = c;
+        for (int d = 1; d < wpc; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (w >= d) incl += o;
+        }
+        base = incl - c;
+    }
+    uint32_t x = 0u;
+    if (info) {
+        const uint32_t* srow = sw + g * nq;
+        const int q0 = base >> 5, sh = base & 31;
+        const uint32_t lo = srow[q0];
+        const uint32_t hi = q0 + 1 < nq ? srow[q0 + 1] : 0u;
+        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
+    }
+    for (int h = 1; h < nb; h <<= 1) x ^= (x >> h) & span_mask(h);  // x = u G_n (my_sn enc.py:85-96)
+    for (int hw = 1; hw < wpc; hw <<= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
+        if ((w & hw) == 0) x ^= other;
+    }
+    cwd[g * wpc + w] = x;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
+    if (rows <= 0) return;
+    // C1: u rows (BinarySource output, float32 0/1)
+    if (u_out != nullptr && k > 0) {
+        if ((k & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
+            const int kq = k >> 2;
+            for (int c = lane; c < rows * kq; c += 64) {
+                const int r = c / kq, p = (c - r * kq) * 4;
+                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
+                reinterpret_cast<float4*>(u_out + (b0 + r) * k)[p >> 2] =
+                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
+            }
+        } else {
+            for (int c = lane; c < rows * k; c += 64) {
+                const int r = c / k, p = c - r * k;
+                u_out[(b0 + r) * k + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
+            }
+        }
+    }
+    // C1': the information bits packed (awgn_llr_kernel's layout), bits past k cleared
+    if (ubits_out != nullptr && k > 0) {
+        const uint32_t last = (k & 31) ? ((1u << (k & 31)) - 1u) : 0xFFFFFFFFu;
+        for (int r = 0; r < rows; ++r)
+            for (int q = lane; q < nq; q += 64) ubits_out[(b0 + r) * nq + q] = sw[r * nq + q] & (q == nq - 1 ? last : 0xFFFFFFFFu);
+    }
+    // C2: y = x + sqrt(no) * N(0, 1/2) per component (awgn.py:24-29, utils.py:11-15), the demapper.
+    // Pair pc of a row = positions [2M pc, 2M pc + 2M) (n >= 2M: inside one code word, M = 4, 8),
+    // noise block pc; with one symbol per row (n = M) the pair's second half is unused.
+    const float inv_no = 1.0f / no, rsig = sqrtf(no) * 0.70710677f * 1.17741002f;  // sqrt(2 ln 2)
+    const int ns = n / M, npair = (ns + 1) >> 1;
+    const bool vec = (reinterpret_cast<uintptr_t>(llr_out) & 15) == 0;
+    for (int c = lane; c < rows * npair; c += 64) {
+        const int r = c / npair, pc = c - r * npair, p = pc * 2 * M;
+        const U4 rnd = stream_block(k0, k1, row0 + b0 + r, it, 1, (uint32_t)pc);
+        const float4 y = qam_receive<M>(rnd, cwd[r * wpc + (p >> 5)] >> (p & 31), s_lev, rsig);
+#pragma unroll 1
+        for (int s = 0; s < 2; ++s) {
+            const int sym = 2 * pc + s;
+            if (sym >= ns) break;
+            const float yr = s ? y.z : y.x, yi = s ? y.w : y.y;
+            float l[M];
+            qam_axis_llr<M / 2>(yr, qam.lev, qam.d, qam.inv2d, inv_no, l);
+            qam_axis_llr<M / 2>(yi, qam.lev, qam.d, qam.inv2d, inv_no, l + 1);
+            float* o = llr_out + (b0 + r) * n + sym * M;
+            if (vec) {
+#pragma unroll
+                for (int i = 0; i < M; i += 4) *reinterpret_cast<float4*>(o + i) = float4{l[i], l[i + 1], l[i + 2], l[i + 3]};
+            } else {
+#pragma unroll
+                for (int i = 0; i < M; ++i) o[i] = l[i];
+            }
+            if (y_out != nullptr) {
+                float* yo = y_out + ((b0 + r) * ns + sym) * 2;
+                yo[0] = yr, yo[1] = yi;
+            }
+        }
+    }
+}
+
+// nr_awgn_qam_llr_kernel<M>: nr_awgn_llr_kernel with a 2^M-QAM mapper and demapper (M = 4, 6, 8; M
+// divides E).  Phases A, A', B, C1, C1' and C3 are nr_awgn_llr_kernel's; C2 takes the wave's lanes over
+// (row, symbol pair): transmitted positions 2M pc .. 2M pc + 2M - 1 (bit e = c[rm_idx[e]]), noise block
+// pc of domain 1; with an odd symbol count the last pair's second half is unused.  The stage rows
+// are 4 ceil(E/4) floats as there, so rows per pass and the LDS budget are unchanged.
+// y_out (nullable): [bs, E / M, 2] fp32 received symbols (re, im).
+template <int M>
+__global__ __launch_bounds__(256) void nr_awgn_qam_llr_kernel(
+    int64_t bs, int64_t row0, uint32_t k0, uint32_t k1, uint32_t it, float no, const uint32_t* __restrict__ frozen_words,
+    int n, int k, int kt, const uint32_t* __restrict__ g_rows, int degree, const int32_t* __restrict__ rm_idx, int e_len,
+    const int32_t* __restrict__ src_a, const int32_t* __restrict__ src_b, const float* __restrict__ fill, Qam qam,
+    float* __restrict__ u_out, uint32_t* __restrict__ ubits_out, float* __restrict__ llr_ch_out,
+    float* __restrict__ llr_out, float* __restrict__ y_out) {
+    __shared__ uint32_t s_g[kNrGWords];
+    __shared__ uint32_t lds[4 * 192];
+    __shared__ __attribute__((aligned(16))) float s_stage[4 * kNrStage];
+    __shared__ float s_lev[16];
+    const int wpc = n / 32, cpw = 64 / wpc;
+    const int nq = (kt + 31) / 32, nkq = (k + 31) / 32;  // words of the information bits / with the parity
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
+    uint32_t* sw = lds + wv * 192;                             // [cpw][nq] stream words
+    uint32_t* kw = sw + 64;                                    // [cpw][nkq] information bits | parity
+    uint32_t* cwd = sw + 128;                                  // [cpw][wpc] code words
+    float* st = s_stage + wv * kNrStage;
+    const int g = lane / wpc, w = lane % wpc;
+    const int64_t row = row0 + b0 + g;
+
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int a = 0; a < 16; ++a) s_lev[a] = qam.lev[a];
+    }
+    for (int m = threadIdx.x; m < kt; m += 256) s_g[m + (m >> 5)] = g_rows[m];
+    // A: stream words (rows past bs compute harmless values that are never stored)
+    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
+    __syncthreads();
+
+    // A': parity of the row; nq <= wpc (kt < n), so lane w < nq owns word w of its row
+    const uint32_t last = (kt & 31) ? ((1u << (kt & 31)) - 1u) : 0xFFFFFFFFu;
+    const uint32_t mine = w < nq ? sw[g * nq + w] & (w == nq - 1 ? last : 0xFFFFFFFFu) : 0u;
+    uint32_t par = 0u;
+    {
+        const uint32_t* gr = s_g + w * 33;
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j)
+            if ((mine >> j) & 1u) par ^= gr[j];
+    }
+    for (int d = 1; d < wpc; d <<= 1) par ^= (uint32_t)__shfl_xor((int)par, d, 64);
+    if (degree < 32) par &= (1u << degree) - 1u;
+    if (w < nkq) {
+        const uint64_t pv = (uint64_t)par << (kt & 31);  // parity bit c = bit kt + c of the row
+        const int pw = kt >> 5;
+        kw[g * nkq + w] = mine | (w == pw ? (uint32_t)pv : 0u) | (w == pw + 1 ? (uint32_t)(pv >> 32) : 0u);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    // B: the k bits deposited at the information positions, XOR butterfly (awgn_llr_kernel's B)
+    const uint32_t info = ~frozen_words[w];
+    int base = 0;
+    {
+        int c = __popc(info), incl = c;
+        for (int d = 1; d < wpc; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (w >= d) incl += o;
+        }
+        base = incl - c;
+    }
+    uint32_t x = 0u;
+    if (info) {
+        const uint32_t* srow = kw + g * nkq;
+        const int q0 = base >> 5, sh = base & 31;
+        const uint32_t lo = q0 < nkq ? srow[q0] : 0u;
+        const uint32_t hi = q0 + 1 < nkq ? srow[q0 + 1] : 0u;
+        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
+    }
+    for (int h = 1; h < 32; h <<= 1) x ^= (x >> h) & span_mask(h);
+    for (int hw = 1; hw < wpc; hw <<= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
+        if ((w & hw) == 0) x ^= other;
+    }
+    cwd[g * wpc + w] = x;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
+    if (rows <= 0) return;
+    // C1: u rows (BinarySource output, float32 0/1)
+    if (u_out != nullptr && kt > 0) {
+        if ((kt & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
+            const int kq = kt >> 2;
+            for (int c = lane; c < rows * kq; c += 64) {
+                const int r = c / kq, p = (c - r * kq) * 4;
+                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
+                reinterpret_cast<float4*>(u_out + (b0 + r) * kt)[p >> 2] =
+                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
+            }
+        } else {
+            for (int c = lane; c < rows * kt; c += 64) {
+                const int r = c / kt, p = c - r * kt;
+                u_out[(b0 + r) * kt + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
+            }
+        }
+    }
+    // C1': the information bits packed (pl_count_errors_packed's reference), bits past kt cleared
+    if (ubits_out != nullptr)
+        for (int c = lane; c < rows * nq; c += 64) {
+            const int q = c % nq;
+            ubits_out[b0 * nq + c] = sw[c] & (q == nq - 1 ? last : 0xFFFFFFFFu);
+        }
+
+    const float inv_no = 1.0f / no, rsig = sqrtf(no) * 0.70710677f * 1.17741002f;  // sqrt(2 ln 2)
+    const int ns = e_len / M, npair = (ns + 1) >> 1;  // symbols and symbol pairs per row
+    const int epad = ((e_len + 3) >> 2) * 4;
+    const int rpp = kNrStage / epad < cpw ? kNrStage / epad : cpw;  // rows per pass (>= 1: E <= kNrStage)
+    const bool idx_vec = (reinterpret_cast<uintptr_t>(rm_idx) & 15) == 0;
+    const bool tab_vec = ((reinterpret_cast<uintptr_t>(src_a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(src_b) & 15) == 0) &&
+                         ((reinterpret_cast<uintptr_t>(fill) & 15) == 0) && ((reinterpret_cast<uintptr_t>(llr_out) & 15) == 0);
+    const int nj = n >> 2, lnj = __builtin_ctz(nj);
+    for (int r0 = 0; r0 < rows; r0 += rpp) {
+        const int rc = rows - r0 < rpp ? rows - r0 : rpp;
+        // C2: rate matching, QAM, AWGN, demapper -> stage (+ llr_ch_out, y_out)
+        for (int c = lane; c < rc * npair; c += 64) {
+            const int rl = c / npair, pc = c - rl * npair, r = r0 + rl, p = pc * 2 * M;
+            int id[2 * M];
+            if (idx_vec && p + 2 * M <= e_len) {
+#pragma unroll
+                for (int i = 0; i < 2 * M; i += 4) {
+                    const int4 v = *reinterpret_cast<const int4*>(rm_idx + p + i);
+                    id[i] = v.x, id[i + 1] = v.y, id[i + 2] = v.z, id[i + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2 * M; ++i) id[i] = p + i < e_len ? rm_idx[p + i] : 0;
+            }
+            const uint32_t* cw = cwd + r * wpc;
+            uint32_t bits = 0u;
+#pragma unroll
+            for (int i = 0; i < 2 * M; ++i) {
+                const int j = id[i] & (n - 1);  // a table entry outside the codeword cannot leave the row
+                bits |= ((cw[j >> 5] >> (j & 31)) & 1u) << i;
+            }
+            const U4 rnd = stream_block(k0, k1, row0 + b0 + r, it, 1, (uint32_t)pc);
+            const float4 y = qam_receive<M>(rnd, bits, s_lev, rsig);
+#pragma unroll 1
+            for (int s = 0; s < 2; ++s) {
+                const int sym = 2 * pc + s;
+                if (sym >= ns) break;
+                const float yr = s ? y.z : y.x, yi = s ? y.w : y.y;
+                float l[M];
+                qam_axis_llr<M / 2>(yr, s_lev, qam.d, qam.inv2d, inv_no, l);
+                qam_axis_llr<M / 2>(yi, s_lev, qam.d, qam.inv2d, inv_no, l + 1);
+                float* so = st + rl * epad + sym * M;  // an even offset: 8-byte stores
+#pragma unroll
+                for (int i = 0; i < M; i += 2) *reinterpret_cast<float2*>(so + i) = float2{l[i], l[i + 1]};
+                if (llr_ch_out != nullptr) {
+                    float* o = llr_ch_out + (b0 + r) * e_len + sym * M;  // a test output: plain stores
+#pragma unroll
+                    for (int i = 0; i < M; ++i) o[i] = l[i];
+                }
+                if (y_out != nullptr) {
+                    float* yo = y_out + ((b0 + r) * ns + sym) * 2;
+                    yo[0] = yr, yo[1] = yi;
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // C3: rate recovery (pl_rate_recover's tables and arithmetic) from the stage
+        for (int c = lane; c < rc * nj; c += 64) {
+            const int rl = c >> lnj, jc = c & (nj - 1), r = r0 + rl;
+            int a[4], b[4];
+            float f[4];
+            if (tab_vec) {
+                const int4 va = reinterpret_cast<const int4*>(src_a)[jc];
+                a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
+                b[0] = b[1] = b[2] = b[3] = -1;
+                if (src_b != nullptr) {
+                    const int4 vb = reinterpret_cast<const int4*>(src_b)[jc];
+                    b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
+                }
+                f[0] = f[1] = f[2] = f[3] = 0.0f;
+                if (fill != nullptr) {
+                    const float4 vf = reinterpret_cast<const float4*>(fill)[jc];
+                    f[0] = vf.x, f[1] = vf.y, f[2] = vf.z, f[3] = vf.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    a[i] = src_a[jc * 4 + i];
+                    b[i] = src_b ? src_b[jc * 4 + i] : -1;
+                    f[i] = fill ? fill[jc * 4 + i] : 0.0f;
+                }
+            }
+            const float* x4 = st + rl * epad;
+            float v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // entries past E - 1 are clamped: a bad table reads another position, never another row
+                const int ia = a[i] < e_len ? a[i] : e_len - 1, ib = b[i] < e_len ? b[i] : e_len - 1;
+                v[i] = f[i];
+                if (ia >= 0) v[i] = ib >= 0 ? x4[ia] + x4[ib] : x4[ia];  // llr_1 + llr_3 (dec.py:629-633)
+            }
+            float* o = llr_out + (b0 + r) * n + jc * 4;
+            if (tab_vec) {
+                *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = v[i];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
 constexpr int kRowsPerWave = 8;  // rows a wave of the counting kernels takes
 
 // Bit and block errors of the first k_cmp columns of [rows, row_len] decided bits (fp32 0/1 or
@@ -685,6 +1116,123 @@ int pl_nr_awgn_qpsk_llr(const pl_plan* p, int32_t k_target, const uint32_t* g_ro
                        row0, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n,
                        p->k, k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, u_out, ubits_out, llr_ch_out,
                        llr_out);
+    return pl::check_hip(hipGetLastError(), what);
+}
+
+// The checks pl_awgn_qam_llr and pl_nr_awgn_qam_llr share, each naming its argument; the ones that
+// need no plan come first.
+static int qam_common_checks(const char* what, int32_t m, int64_t bs, int64_t row0, float no, uint64_t iteration,
+                             const float* y_out, const float* llr_out) {
+    const std::string w(what);
+    if (m != 2 && m != 4 && m != 6 && m != 8) {
+        pl::set_error(w + ": bits_per_symbol must be 2, 4, 6 or 8, got " + std::to_string(m));
+        return PL_EINVAL;
+    }
+    if (m == 2 && y_out) {
+        pl::set_error(w + ": y_out must be NULL with bits_per_symbol 2 (the QPSK kernels do not write it)");
+        return PL_EINVAL;
+    }
+    if (bs < 0 || row0 < 0) {
+        pl::set_error(w + ": bs and row0 must be >= 0");
+        return PL_EINVAL;
+    }
+    if (!(no > 0.0f)) {
+        pl::set_error(w + ": no must be > 0");
+        return PL_EINVAL;
+    }
+    if ((iteration >> 32) != 0) {
+        pl::set_error(w + ": iteration must be < 2^32");
+        return PL_EINVAL;
+    }
+    if (bs > 0 && !llr_out) {
+        pl::set_error(w + ": llr_out must be given");
+        return PL_EINVAL;
+    }
+    return PL_OK;
+}
+
+int pl_awgn_qam_llr(const pl_plan* p, int32_t bits_per_symbol, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs,
+                    float no, float* u_out, uint32_t* ubits_out, float* y_out, float* llr_out, void* stream) {
+    const char* what = "pl_awgn_qam_llr";
+    const int m = bits_per_symbol;
+    if (int r = qam_common_checks(what, m, bs, row0, no, iteration, y_out, llr_out)) return r;
+    if (!p) {
+        pl::set_error(std::string(what) + ": plan must be given");
+        return PL_EINVAL;
+    }
+    if (m == 2) return awgn_launch(p, seed, iteration, row0, bs, no, u_out, ubits_out, llr_out, stream, what);
+    if (p->n % m != 0 || p->n > 2048) {
+        pl::set_error(std::string(what) + ": bits_per_symbol " + std::to_string(m) + " must divide the code length n = " +
+                      std::to_string(p->n) + " (n <= 2048)");
+        return PL_EINVAL;
+    }
+    if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
+    if (bs == 0) return PL_OK;
+    const int wpc = p->n >= 32 ? p->n / 32 : 1;
+    const int64_t cpw = 64 / wpc;
+    const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
+    if (blocks > 0x7fffffffLL) {
+        pl::set_error(std::string(what) + ": batch too large for one launch");
+        return PL_EINVAL;
+    }
+    Qam q;
+    pl::qam_levels(m, q.lev, &q.d);
+    q.inv2d = 1.0f / (2.0f * q.d);
+    auto* kern = m == 4 ? awgn_qam_llr_kernel<4> : awgn_qam_llr_kernel<8>;  // 6 never divides a power of two
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k, q,
+                       u_out, llr_out, ubits_out, y_out);
+    return pl::check_hip(hipGetLastError(), what);
+}
+
+int pl_nr_awgn_qam_llr(const pl_plan* p, int32_t bits_per_symbol, int32_t k_target, const uint32_t* g_rows,
+                       int32_t crc_degree, const int32_t* rm_idx, int32_t e, const int32_t* src_a, const int32_t* src_b,
+                       const float* fill, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no,
+                       uint32_t* ubits_out, float* u_out, float* y_out, float* llr_ch_out, float* llr_out, void* stream) {
+    const char* what = "pl_nr_awgn_qam_llr";
+    const int m = bits_per_symbol;
+    if (int r = qam_common_checks(what, m, bs, row0, no, iteration, y_out, llr_out)) return r;
+    if (m == 2)
+        return pl_nr_awgn_qpsk_llr(p, k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, seed, iteration, row0, bs,
+                                   no, ubits_out, u_out, llr_ch_out, llr_out, stream);
+    if (e < m || e % m != 0 || e > kNrStage) {
+        pl::set_error(std::string(what) + ": E must be a multiple of bits_per_symbol " + std::to_string(m) +
+                      " (whole symbols), " + std::to_string(m) + " ... " + std::to_string(kNrStage) + ", got " +
+                      std::to_string(e));
+        return PL_EINVAL;
+    }
+    if (!p) {
+        pl::set_error(std::string(what) + ": plan must be given");
+        return PL_EINVAL;
+    }
+    if (p->n < 32 || p->n > 1024) {
+        pl::set_error(std::string(what) + ": the mother code length must be 32 ... 1024");
+        return PL_EINVAL;
+    }
+    if (k_target < 0 || crc_degree < 1 || crc_degree > 32 || p->k != k_target + crc_degree) {
+        pl::set_error(std::string(what) + ": the plan's k must equal k_target + crc_degree (crc_degree 1 ... 32)");
+        return PL_EINVAL;
+    }
+    if (bs > 0 && (!rm_idx || !src_a || (k_target > 0 && !g_rows))) {
+        pl::set_error(std::string(what) + ": g_rows, rm_idx and src_a must be given");
+        return PL_EINVAL;
+    }
+    if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
+    if (bs == 0) return PL_OK;
+    const int64_t cpw = 64 / (p->n / 32);
+    const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
+    if (blocks > 0x7fffffffLL) {
+        pl::set_error(std::string(what) + ": batch too large for one launch");
+        return PL_EINVAL;
+    }
+    Qam q;
+    pl::qam_levels(m, q.lev, &q.d);
+    q.inv2d = 1.0f / (2.0f * q.d);
+    auto* kern = m == 4 ? nr_awgn_qam_llr_kernel<4> : m == 6 ? nr_awgn_qam_llr_kernel<6> : nr_awgn_qam_llr_kernel<8>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k,
+                       k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, q, u_out, ubits_out, llr_ch_out,
+                       llr_out, y_out);
     return pl::check_hip(hipGetLastError(), what);
 }
 

@@ -68,4 +68,7 @@ int launch_sc_static_sim(const pl_plan* plan, uint64_t seed, uint64_t iteration,
                          int32_t* part, float* llr_dump, float* u_dump, hipStream_t stream);
 // counts[0..1] += the sums of the [bit, block] pairs of part (channel_kernel.hip)
 int launch_sum_pairs(const int32_t* part, int64_t pairs, int64_t* counts, hipStream_t stream);
+// The 2^(m/2) Gray PAM levels of unit-energy 2^m-QAM (m = 2, 4, 6, 8), indexed by the axis label
+// (first bit most significant), the rest of lev[16] zero; *d = the smallest positive level; capi.cpp
+void qam_levels(int bits_per_symbol, float lev[16], float* d);
 }  // namespace pl

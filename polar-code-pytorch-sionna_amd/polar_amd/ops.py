@@ -274,6 +274,88 @@ def nr_awgn_qpsk_llr(plan, k_target, g_rows, crc_degree, rm_idx, src_a, src_b, f
     return u, ubits, ch, llr
 
 
+QAM_BITS_PER_SYMBOL = (2, 4, 6, 8)  # what the fused producers modulate: QPSK, 16-, 64-, 256-QAM
+
+
+def check_bits_per_symbol(m, positions, what):
+    """ValueError unless m is one of QAM_BITS_PER_SYMBOL and divides the row's `positions` (`what`
+    names them: the code length n, or the transmitted length E)."""
+    if m not in QAM_BITS_PER_SYMBOL:
+        raise ValueError(f"num_bits_per_symbol must be one of {QAM_BITS_PER_SYMBOL}, got {m}")
+    if int(positions) % m != 0:
+        raise ValueError(f"num_bits_per_symbol {m} must divide {what} = {positions} (whole symbols)")
+    return int(m)
+
+
+def awgn_qam_llr(plan, bits_per_symbol, bs, no, seed, iteration, row0=0, with_u=True, with_ubits=False, with_y=False):
+    """The fused System_AWGN_model producer over 2^m-QAM (pl_awgn_qam_llr), m = bits_per_symbol in
+    {2, 4, 6, 8} dividing plan.n, on the plan's device: returns (u [bs, k] fp32 0/1 or None, ubits
+    [bs, ceil(k/32)] int32 or None, y [bs, n/m, 2] fp32 received symbols or None, logits [bs, n]
+    fp32) for rows row0.. of the (seed, iteration) stream, the optional ones as with_u / with_ubits
+    / with_y say (with_y needs m > 2).  The information bits are awgn_qpsk_llr's for the same key."""
+    dev = plan.device
+    no, bs = float(no), int(bs)
+    m = check_bits_per_symbol(bits_per_symbol, plan.n, "the code length n")
+    if not no > 0.0:
+        raise ValueError(f"noise variance must be positive, got {no}")
+    if not 0 <= int(iteration) < 2 ** 32:
+        raise ValueError(f"iteration must be in [0, 2^32) (the Philox counter word), got {iteration}")
+    if bs < 0:
+        raise ValueError(f"bs must be >= 0, got {bs}")
+    if with_y and m == 2:
+        raise ValueError("with_y needs num_bits_per_symbol > 2 (the QPSK kernel does not write the symbols)")
+    llr = torch.empty((bs, plan.n), dtype=torch.float32, device=dev)
+    u = torch.empty((bs, plan.k), dtype=torch.float32, device=dev) if with_u else None
+    ubits = torch.empty((bs, (plan.k + 31) // 32), dtype=torch.int32, device=dev) if with_ubits else None
+    y = torch.empty((bs, plan.n // m, 2), dtype=torch.float32, device=dev) if with_y else None
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pl_awgn_qam_llr(plan.handle, m, int(seed) & (2 ** 64 - 1), int(iteration) & (2 ** 64 - 1),
+                                              int(row0), bs, no, ptr(u), ptr(ubits), ptr(y), ptr(llr),
+                                              _lib.current_stream_ptr(dev)), "pl_awgn_qam_llr")
+    return u, ubits, y, llr
+
+
+def nr_awgn_qam_llr(plan, bits_per_symbol, k_target, g_rows, crc_degree, rm_idx, src_a, src_b, fill, bs, no, seed,
+                    iteration, row0=0, with_u=True, with_ubits=True, with_ch=False, with_y=False):
+    """The fused 5G NR link producer over 2^m-QAM (pl_nr_awgn_qam_llr), m = bits_per_symbol in
+    {2, 4, 6, 8} dividing E = len(rm_idx): nr_awgn_qpsk_llr's arguments and outputs, plus y [bs, E/m, 2]
+    fp32 received symbols (with_y, m > 2).  Returns (u, ubits, llr_ch, y, llr)."""
+    dev = plan.device
+    k_target, bs = int(k_target), int(bs)
+    if k_target < 0 or bs < 0:
+        raise ValueError(f"k_target and bs must be >= 0, got {k_target}, {bs}")
+    if not isinstance(rm_idx, torch.Tensor) or rm_idx.dim() != 1:
+        raise ValueError("rm_idx must be a 1-D int32 tensor (the rate-matching gather index)")
+    e = int(rm_idx.numel())
+    m = check_bits_per_symbol(bits_per_symbol, e, "the transmitted length E")
+    if with_y and m == 2:
+        raise ValueError("with_y needs num_bits_per_symbol > 2 (the QPSK kernel does not write the symbols)")
+    g_rows = _table(g_rows, torch.int32, k_target, "g_rows", dev)
+    rm_idx = _table(rm_idx, torch.int32, e, "rm_idx", dev)
+    src_a = _table(src_a, torch.int32, plan.n, "src_a", dev)
+    src_b = _table(src_b, torch.int32, plan.n, "src_b", dev, optional=True)
+    fill = _table(fill, torch.float32, plan.n, "fill", dev, optional=True)
+    nq = (k_target + 31) // 32
+    llr = torch.empty((bs, plan.n), dtype=torch.float32, device=dev)
+    u = torch.empty((bs, k_target), dtype=torch.float32, device=dev) if with_u else None
+    ubits = torch.empty((bs, nq), dtype=torch.int32, device=dev) if with_ubits else None
+    ch = torch.empty((bs, e), dtype=torch.float32, device=dev) if with_ch else None
+    y = torch.empty((bs, e // m, 2), dtype=torch.float32, device=dev) if with_y else None
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pl_nr_awgn_qam_llr(plan.handle, m, k_target, ptr(g_rows), int(crc_degree), ptr(rm_idx), e,
+                                                 ptr(src_a), ptr(src_b), ptr(fill), int(seed) & (2 ** 64 - 1),
+                                                 int(iteration) & (2 ** 64 - 1), int(row0), bs, float(no),
+                                                 ptr(ubits), ptr(u), ptr(y), ptr(ch), ptr(llr),
+                                                 _lib.current_stream_ptr(dev)), "pl_nr_awgn_qam_llr")
+    return u, ubits, ch, y, llr
+
+
 def count_errors_packed(bits, ref_bits, k_cmp=None, counts=None):
     """pl_count_errors_packed: [bit errors, block errors] (int64, on the device) of the first k_cmp
     columns (default: all) of `bits` ([bs, row_len] fp32 0/1 or uint8, e.g. a decoder's k_polar-wide
