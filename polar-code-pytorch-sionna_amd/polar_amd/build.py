@@ -121,7 +121,8 @@ def build(force=False, verbose=False, dev=False):
     os.makedirs(obj_dir, exist_ok=True)
     inc = _embed_static_source()
     hash_h = _write_src_hash(obj_dir)
-    deps = [os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "softplus.h"), os.path.join(CSRC, "exactf.h"),
+    deps = [os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "butterfly.h"), os.path.join(CSRC, "softplus.h"),
+            os.path.join(CSRC, "exactf.h"),
             os.path.join(CSRC, "hybrid.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
     jobs = []
     for oname, s, defs in UNITS:

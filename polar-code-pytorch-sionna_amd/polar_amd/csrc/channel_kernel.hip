@@ -27,6 +27,7 @@
 #include <string>
 
 #include "../../../include/polar_mi355x.h"
+#include "butterfly.h"
 #include "plan.h"
 
 namespace {
@@ -49,17 +50,6 @@ __device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
         k1 += 0xBB67AE85u;
     }
     return c;
-}
-
-
-__device__ __forceinline__ uint32_t span_mask(int h) {
-    switch (h) {
-        case 1: return 0x55555555u;
-        case 2: return 0x33333333u;
-        case 4: return 0x0f0f0f0fu;
-        case 8: return 0x00ff00ffu;
-        default: return 0x0000ffffu;  // 16
-    }
 }
 
 // Parallel bit deposit: bit i of x goes to the position of the i-th set bit of m (Hacker's
@@ -96,31 +86,48 @@ struct Logit {
     float rsc;  // scale * sqrt(no / 2) * sqrt(2 ln 2)
 };
 
-// Four logits from one Philox block and the four code bits in bits 0..3 of `bits`.  Box-Muller on
-// the hardware transcendentals (a noise draw, not a decoder value: only its distribution is
-// specified):
+#ifndef PL_AWGN_DIAG
+#define PL_AWGN_DIAG 0  // development only (tools/micro/producer_cost.hip): 1 no logit stores,
+                        // 2 no noise (Philox + Box-Muller), 3 no Philox for the noise
+#endif
+#if !PL_DEV && PL_AWGN_DIAG
+#error "PL_AWGN_DIAG gives wrong results: development builds (-DPL_DEV=1) only"
+#endif
+
+// Two Box-Muller pairs from one Philox block, on the hardware transcendentals (a noise draw, not a
+// decoder value: only its distribution is specified); the noise of a pair is rs * (c, s).
 //   radius  sqrt(-2 ln u) = sqrt(2 ln 2) sqrt(32 - log2 v'), v' = float(v | 1) in [1, 2^32], i.e.
-//           u = v' 2^-32 in (0, 1] (tail to 6.66 sigma), v_log_f32 on a normal argument;
+//           u = v' 2^-32 in (0, 1] (tail to 6.66 sigma), v_log_f32 on a normal argument; rsc carries
+//           the sqrt(2 ln 2) and the caller's scale;
 //   angle   v_sin / v_cos take revolutions and are periodic: the mantissa bits of v under the
 //           exponent of 1.0 give 1 + t, t uniform in [0, 1), and sin(2 pi (1 + t)) = sin(2 pi t).
-__device__ __forceinline__ float4 logits4(const U4& rnd, uint32_t bits, const Logit& lc) {
+struct Gauss4 {
+    float rs0, c0, s0;  // components x, y of the block
+    float rs1, c1, s1;  // components z, w
+};
+__device__ __forceinline__ Gauss4 box_muller(const U4& rnd, float rsc) {
 #if PL_AWGN_DIAG == 2
-    const float c0 = (float)rnd.x, s0 = (float)rnd.y, c1 = (float)rnd.z, s1 = 1.0f, rs0 = lc.rsc, rs1 = lc.rsc;
+    return Gauss4{rsc, (float)rnd.x, (float)rnd.y, rsc, (float)rnd.z, 1.0f};
 #else
-    const float rs0 = lc.rsc * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.x | 1u)));
-    const float rs1 = lc.rsc * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.z | 1u)));
+    const float rs0 = rsc * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.x | 1u)));
+    const float rs1 = rsc * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.z | 1u)));
     const float t0 = __uint_as_float(0x3F800000u | (rnd.y >> 9)), t1 = __uint_as_float(0x3F800000u | (rnd.w >> 9));
-    const float c0 = __builtin_amdgcn_cosf(t0), s0 = __builtin_amdgcn_sinf(t0);
-    const float c1 = __builtin_amdgcn_cosf(t1), s1 = __builtin_amdgcn_sinf(t1);
+    return Gauss4{rs0, __builtin_amdgcn_cosf(t0), __builtin_amdgcn_sinf(t0), rs1, __builtin_amdgcn_cosf(t1),
+                  __builtin_amdgcn_sinf(t1)};
 #endif
+}
+
+// Four logits from one Philox block and the four code bits in bits 0..3 of `bits`.
+__device__ __forceinline__ float4 logits4(const U4& rnd, uint32_t bits, const Logit& lc) {
+    const Gauss4 g = box_muller(rnd, lc.rsc);
     // (1 - 2 c) a: the code bit moved to the sign of a
     const uint32_t au = __float_as_uint(lc.a);
     const float a0 = __uint_as_float(au ^ ((bits << 31) & 0x80000000u));
     const float a1 = __uint_as_float(au ^ ((bits << 30) & 0x80000000u));
     const float a2 = __uint_as_float(au ^ ((bits << 29) & 0x80000000u));
     const float a3 = __uint_as_float(au ^ ((bits << 28) & 0x80000000u));
-    return float4{__builtin_fmaf(rs0, c0, a0), __builtin_fmaf(rs0, s0, a1), __builtin_fmaf(rs1, c1, a2),
-                  __builtin_fmaf(rs1, s1, a3)};
+    return float4{__builtin_fmaf(g.rs0, g.c0, a0), __builtin_fmaf(g.rs0, g.s0, a1), __builtin_fmaf(g.rs1, g.c1, a2),
+                  __builtin_fmaf(g.rs1, g.s1, a3)};
 }
 
 // A wave holds cpw = 64 / wpc codewords (wpc = max(1, n/32) lanes per codeword).  Three phases:
@@ -130,94 +137,121 @@ __device__ __forceinline__ float4 logits4(const U4& rnd, uint32_t bits, const Lo
 //   C  the whole wave over the wave's rows in chunks of CH = min(4, n) positions ("chunk layout",
 //      consecutive lanes -> consecutive chunks, so the fp32 rows are written as whole lines):
 //      u rows from the stream words, logit rows from the code bits and one Philox block per chunk.
-constexpr int kWordsPerWave = 256;
-#ifndef PL_AWGN_DIAG
-#define PL_AWGN_DIAG 0  // development only (tools/micro/producer_cost.hip): 1 no logit stores,
-                        // 2 no noise (Philox + Box-Muller), 3 no Philox for the noise
-#endif  // LDS words per wave: stream words (<= 128) + code words (64)
-#if !PL_DEV && PL_AWGN_DIAG
-#error "PL_AWGN_DIAG gives wrong results: development builds (-DPL_DEV=1) only"
-#endif
+// The four producer kernels below are sequences of these phases, one function each.
+constexpr int kWordsPerWave = 256;  // LDS words per wave: stream words (<= 128) + code words (64)
+
+// What one wave wrote to LDS, every lane of the wave may read after this.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The layout above for a code of n positions (a power of two), as every producer derives it
+struct WaveRows {
+    int lane, wv;      // lane of the wave, wave of the block
+    int wpc, cpw, nb;  // lanes (words) per codeword, codewords per wave, positions per word
+    int g, w;          // this lane's codeword of the wave and word of the codeword
+    int64_t b0, row;   // first row of this wave (of the call), stream row of this lane's codeword
+    int rows;          // rows of this wave to store (<= 0: none)
+};
+__device__ __forceinline__ WaveRows wave_rows(int n, int64_t row0, int64_t bs) {
+    WaveRows L;
+    L.wpc = n >= 32 ? n / 32 : 1, L.cpw = 64 / L.wpc, L.nb = n >= 32 ? 32 : n;
+    L.lane = threadIdx.x & 63, L.wv = threadIdx.x >> 6;
+    L.b0 = ((int64_t)blockIdx.x * 4 + L.wv) * L.cpw;
+    L.g = L.lane / L.wpc, L.w = L.lane % L.wpc;
+    L.row = row0 + L.b0 + L.g;
+    L.rows = bs - L.b0 < L.cpw ? (int)(bs - L.b0) : L.cpw;
+    return L;
+}
+
+// A: the nq stream words of this lane's row -> sw [cpw][nq] (rows past bs compute harmless values
+// that are never stored)
+__device__ __forceinline__ void draw_stream_words(uint32_t* sw, int nq, const WaveRows& L, uint32_t k0, uint32_t k1,
+                                                  uint32_t it) {
+    for (int q = L.w; q < nq; q += L.wpc) sw[L.g * nq + q] = comp(stream_block(k0, k1, L.row, it, 0, q >> 2), q & 3);
+}
+
+// B: this lane's code word from its row's bits (src [cpw][nsrc] words).  Information positions of
+// the word (frozen bit 0), their first rank = information positions in the group's earlier words
+// (prefix sum over the group's lanes); the next (up to 32) bits of the row deposited at them in
+// order; x = u G_n.
+__device__ __forceinline__ uint32_t encode_word(const uint32_t* src, int nsrc, const uint32_t* __restrict__ frozen_words,
+                                                const WaveRows& L) {
+    const uint32_t live = L.nb == 32 ? 0xFFFFFFFFu : ((1u << L.nb) - 1u);
+    const uint32_t info = ~frozen_words[L.w] & live;
+    int base = 0;
+    {
+        int c = __popc(info), incl = c;
+        for (int d = 1; d < L.wpc; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if (L.w >= d) incl += o;
+        }
+        base = incl - c;
+    }
+    uint32_t x = 0u;
+    if (info) {
+        const uint32_t* srow = src + L.g * nsrc;
+        const int q0 = base >> 5, sh = base & 31;
+        const uint32_t lo = q0 < nsrc ? srow[q0] : 0u;
+        const uint32_t hi = q0 + 1 < nsrc ? srow[q0 + 1] : 0u;
+        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
+    }
+    return pl::polar_butterfly(x, L.nb, L.wpc, L.w);
+}
+
+// C1: u rows (BinarySource output, float32 0/1) of the wave's rows from sw [cpw][nq]
+__device__ __forceinline__ void store_u_rows(float* __restrict__ u_out, const uint32_t* sw, int nq, int k,
+                                             const WaveRows& L) {
+    if (u_out == nullptr || k <= 0) return;
+    if ((k & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
+        const int kq = k >> 2;
+        for (int c = L.lane; c < L.rows * kq; c += 64) {
+            const int r = c / kq, p = (c - r * kq) * 4;
+            const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
+            reinterpret_cast<float4*>(u_out + (L.b0 + r) * k)[p >> 2] =
+                float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
+        }
+    } else {
+        for (int c = L.lane; c < L.rows * k; c += 64) {
+            const int r = c / k, p = c - r * k;
+            u_out[(L.b0 + r) * k + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
+        }
+    }
+}
+
+// C1': the information bits packed, nq = ceil(k/32) words per row (bit m of a row = bit m % 32 of
+// word m / 32: the stream words themselves, bits past k cleared) -- the reference of
+// pl_sc_decode_count and pl_count_errors_packed, 1/32 of the fp32 rows' bytes
+__device__ __forceinline__ void store_packed_rows(uint32_t* __restrict__ ubits_out, const uint32_t* sw, int nq, int k,
+                                                  const WaveRows& L) {
+    if (ubits_out == nullptr) return;
+    const uint32_t last = (k & 31) ? ((1u << (k & 31)) - 1u) : 0xFFFFFFFFu;
+    for (int r = 0; r < L.rows; ++r)
+        for (int q = L.lane; q < nq; q += 64)
+            ubits_out[(L.b0 + r) * nq + q] = sw[r * nq + q] & (q == nq - 1 ? last : 0xFFFFFFFFu);
+}
 
 __global__ __launch_bounds__(256) void awgn_llr_kernel(int64_t bs, int64_t row0, uint32_t k0, uint32_t k1, uint32_t it,
                                                        float no, const uint32_t* __restrict__ frozen_words, int n, int k,
                                                        float* __restrict__ u_out, float* __restrict__ llr_out,
                                                        uint32_t* __restrict__ ubits_out) {
     __shared__ uint32_t lds[4 * kWordsPerWave];
-    const int wpc = n >= 32 ? n / 32 : 1, cpw = 64 / wpc, nb = n >= 32 ? 32 : n;
-    const int nq = (k + 31) / 32;  // stream words per row
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
-    uint32_t* sw = lds + wv * kWordsPerWave;                   // [cpw][nq] stream words
-    uint32_t* cwd = sw + cpw * nq;                             // [cpw][wpc] code words
-    const int g = lane / wpc, w = lane % wpc;
-    const int64_t row = row0 + b0 + g;
+    const WaveRows L = wave_rows(n, row0, bs);
+    const int nq = (k + 31) / 32;                 // stream words per row
+    uint32_t* sw = lds + L.wv * kWordsPerWave;    // [cpw][nq] stream words
+    uint32_t* cwd = sw + L.cpw * nq;              // [cpw][wpc] code words
+    const int lane = L.lane, wpc = L.wpc, rows = L.rows;
+    const int64_t b0 = L.b0;
 
-    // A: stream words (rows past bs compute harmless values that are never stored)
-    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    // B: information positions of this word (frozen bit 0), their first rank = information
-    // positions in the group's earlier words (prefix sum over the group's lanes)
-    const uint32_t live = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
-    const uint32_t info = ~frozen_words[w] & live;
-    int base = 0;
-    {
-        int c = __popc(info), incl = c;
-        for (int d = 1; d < wpc; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (w >= d) incl += o;
-        }
-        base = incl - c;
-    }
-    uint32_t x = 0u;
-    if (info) {
-        const uint32_t* srow = sw + g * nq;
-        const int q0 = base >> 5, sh = base & 31;
-        const uint32_t lo = srow[q0];
-        const uint32_t hi = q0 + 1 < nq ? srow[q0 + 1] : 0u;
-        // the next (up to 32) information bits, deposited at the information positions in order
-        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
-    }
-    for (int h = 1; h < nb; h <<= 1) x ^= (x >> h) & span_mask(h);  // x = u G_n (my_sn enc.py:85-96)
-    for (int hw = 1; hw < wpc; hw <<= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
-        if ((w & hw) == 0) x ^= other;
-    }
-    cwd[g * wpc + w] = x;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
+    draw_stream_words(sw, nq, L, k0, k1, it);
+    wave_sync();
+    cwd[L.g * wpc + L.w] = encode_word(sw, nq, frozen_words, L);
+    wave_sync();
     if (rows <= 0) return;
-    // C1: u rows (BinarySource output, float32 0/1)
-    if (u_out != nullptr && k > 0) {
-        if ((k & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
-            const int kq = k >> 2;
-            for (int c = lane; c < rows * kq; c += 64) {
-                const int r = c / kq, p = (c - r * kq) * 4;
-                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
-                reinterpret_cast<float4*>(u_out + (b0 + r) * k)[p >> 2] =
-                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
-            }
-        } else {
-            for (int c = lane; c < rows * k; c += 64) {
-                const int r = c / k, p = c - r * k;
-                u_out[(b0 + r) * k + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
-            }
-        }
-    }
-    // C1': the information bits packed, ceil(k/32) words per row (bit m of a row = bit m % 32 of
-    // word m / 32: the stream words themselves, bits past k cleared) -- the decode+count kernel's
-    // reference (pl_sc_decode_count), 1/32 of the fp32 rows' bytes
-    if (ubits_out != nullptr && k > 0) {
-        const uint32_t last = (k & 31) ? ((1u << (k & 31)) - 1u) : 0xFFFFFFFFu;
-        for (int r = 0; r < rows; ++r)
-            for (int q = lane; q < nq; q += 64) ubits_out[(b0 + r) * nq + q] = sw[r * nq + q] & (q == nq - 1 ? last : 0xFFFFFFFFu);
-    }
+    store_u_rows(u_out, sw, nq, k, L);
+    store_packed_rows(ubits_out, sw, nq, k, L);
     // C2: logits.  QPSK component of code bit j: (1 - 2 c_j)/sqrt(2) plus sqrt(no) * N(0, 1/2)
     // (awgn.py:24-29, utils.py:11-15); logit = -2 sqrt(2) y / no.  Chunk c of a row = positions
     // [CH c, CH c + CH) draws noise block c (4 uniforms -> 2 Box-Muller pairs).
@@ -283,32 +317,18 @@ constexpr int kNrStage = 2176;              // stage floats per wave: two rows o
 constexpr int kNrMaxK = 1024;               // generator rows staged per block
 constexpr int kNrGWords = kNrMaxK + kNrMaxK / 32;
 
-__global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
-    int64_t bs, int64_t row0, uint32_t k0, uint32_t k1, uint32_t it, float no, const uint32_t* __restrict__ frozen_words,
-    int n, int k, int kt, const uint32_t* __restrict__ g_rows, int degree, const int32_t* __restrict__ rm_idx, int e_len,
-    const int32_t* __restrict__ src_a, const int32_t* __restrict__ src_b, const float* __restrict__ fill,
-    float* __restrict__ u_out, uint32_t* __restrict__ ubits_out, float* __restrict__ llr_ch_out,
-    float* __restrict__ llr_out) {
-    __shared__ uint32_t s_g[kNrGWords];
-    __shared__ uint32_t lds[4 * 192];
-    __shared__ __attribute__((aligned(16))) float s_stage[4 * kNrStage];
-    const int wpc = n / 32, cpw = 64 / wpc;
-    const int nq = (kt + 31) / 32, nkq = (k + 31) / 32;  // words of the information bits / with the parity
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
-    uint32_t* sw = lds + wv * 192;                             // [cpw][nq] stream words
-    uint32_t* kw = sw + 64;                                    // [cpw][nkq] information bits | parity
-    uint32_t* cwd = sw + 128;                                  // [cpw][wpc] code words
-    float* st = s_stage + wv * kNrStage;
-    const int g = lane / wpc, w = lane % wpc;
-    const int64_t row = row0 + b0 + g;
 
+// The generator rows of the kt information bits -> s_g (row m at word m + m / 32); block-wide, the
+// caller's __syncthreads() follows.
+__device__ __forceinline__ void stage_crc_rows(uint32_t* s_g, const uint32_t* __restrict__ g_rows, int kt) {
     for (int m = threadIdx.x; m < kt; m += 256) s_g[m + (m >> 5)] = g_rows[m];
-    // A: stream words (rows past bs compute harmless values that are never stored)
-    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
-    __syncthreads();
+}
 
-    // A': parity of the row; nq <= wpc (kt < n), so lane w < nq owns word w of its row
+// A': parity of this lane's row from sw [cpw][nq] and the staged generator rows; [information bits |
+// parity] -> kw [cpw][nkq].  nq <= wpc (kt < n), so lane w < nq owns word w of its row.
+__device__ __forceinline__ void crc_attach(uint32_t* kw, int nkq, const uint32_t* sw, int nq, const uint32_t* s_g, int kt,
+                                           int degree, const WaveRows& L) {
+    const int g = L.g, w = L.w;
     const uint32_t last = (kt & 31) ? ((1u << (kt & 31)) - 1u) : 0xFFFFFFFFu;
     const uint32_t mine = w < nq ? sw[g * nq + w] & (w == nq - 1 ? last : 0xFFFFFFFFu) : 0u;
     uint32_t par = 0u;
@@ -318,71 +338,124 @@ __global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
         for (int j = 0; j < 32; ++j)
             if ((mine >> j) & 1u) par ^= gr[j];
     }
-    for (int d = 1; d < wpc; d <<= 1) par ^= (uint32_t)__shfl_xor((int)par, d, 64);
+    for (int d = 1; d < L.wpc; d <<= 1) par ^= (uint32_t)__shfl_xor((int)par, d, 64);
     if (degree < 32) par &= (1u << degree) - 1u;
     if (w < nkq) {
         const uint64_t pv = (uint64_t)par << (kt & 31);  // parity bit c = bit kt + c of the row
         const int pw = kt >> 5;
         kw[g * nkq + w] = mine | (w == pw ? (uint32_t)pv : 0u) | (w == pw + 1 ? (uint32_t)(pv >> 32) : 0u);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
-    // B: the k bits deposited at the information positions, XOR butterfly (awgn_llr_kernel's B)
-    const uint32_t info = ~frozen_words[w];
-    int base = 0;
-    {
-        int c = __popc(info), incl = c;
-        for (int d = 1; d < wpc; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (w >= d) incl += o;
+// Rate matching: the P code bits transmitted at positions p .. p + P - 1 (bit e = c[rm_idx[e]]) of
+// the code word cw [wpc], position p + i in bit i.  vec: rm_idx + p is 16-byte aligned and the P
+// positions lie inside the row.
+template <int P>
+__device__ __forceinline__ uint32_t gather_code_bits(const uint32_t* cw, const int32_t* __restrict__ rm_idx, int p,
+                                                     int e_len, bool vec, int n) {
+    int id[P];
+    if (vec) {
+#pragma unroll
+        for (int i = 0; i < P; i += 4) {
+            const int4 v = *reinterpret_cast<const int4*>(rm_idx + p + i);
+            id[i] = v.x, id[i + 1] = v.y, id[i + 2] = v.z, id[i + 3] = v.w;
         }
-        base = incl - c;
+    } else {
+#pragma unroll
+        for (int i = 0; i < P; ++i) id[i] = p + i < e_len ? rm_idx[p + i] : 0;
     }
-    uint32_t x = 0u;
-    if (info) {
-        const uint32_t* srow = kw + g * nkq;
-        const int q0 = base >> 5, sh = base & 31;
-        const uint32_t lo = q0 < nkq ? srow[q0] : 0u;
-        const uint32_t hi = q0 + 1 < nkq ? srow[q0 + 1] : 0u;
-        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
+    uint32_t bits = 0u;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const int j = id[i] & (n - 1);  // a table entry outside the codeword cannot leave the row
+        bits |= ((cw[j >> 5] >> (j & 31)) & 1u) << i;
     }
-    for (int h = 1; h < 32; h <<= 1) x ^= (x >> h) & span_mask(h);
-    for (int hw = 1; hw < wpc; hw <<= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
-        if ((w & hw) == 0) x ^= other;
-    }
-    cwd[g * wpc + w] = x;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return bits;
+}
 
-    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
-    if (rows <= 0) return;
-    // C1: u rows (BinarySource output, float32 0/1)
-    if (u_out != nullptr && kt > 0) {
-        if ((kt & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
-            const int kq = kt >> 2;
-            for (int c = lane; c < rows * kq; c += 64) {
-                const int r = c / kq, p = (c - r * kq) * 4;
-                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
-                reinterpret_cast<float4*>(u_out + (b0 + r) * kt)[p >> 2] =
-                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
+// C3: rate recovery (pl_rate_recover's tables and arithmetic) of rc rows from the stage (rows of epad
+// floats) to rows r0 .. of the wave, followed by the wave's sync (the next pass rewrites the stage).
+__device__ __forceinline__ void recover_rows(float* __restrict__ llr_out, const float* st, int epad, int e_len, int r0,
+                                             int rc, const int32_t* __restrict__ src_a, const int32_t* __restrict__ src_b,
+                                             const float* __restrict__ fill, int n, const WaveRows& L) {
+    const bool tab_vec = ((reinterpret_cast<uintptr_t>(src_a) & 15) == 0) &&
+                         ((reinterpret_cast<uintptr_t>(src_b) & 15) == 0) &&
+                         ((reinterpret_cast<uintptr_t>(fill) & 15) == 0) && ((reinterpret_cast<uintptr_t>(llr_out) & 15) == 0);
+    const int nj = n >> 2, lnj = __builtin_ctz(nj);
+    for (int c = L.lane; c < rc * nj; c += 64) {
+        const int rl = c >> lnj, jc = c & (nj - 1), r = r0 + rl;
+        int a[4], b[4];
+        float f[4];
+        if (tab_vec) {
+            const int4 va = reinterpret_cast<const int4*>(src_a)[jc];
+            a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
+            b[0] = b[1] = b[2] = b[3] = -1;
+            if (src_b != nullptr) {
+                const int4 vb = reinterpret_cast<const int4*>(src_b)[jc];
+                b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
+            }
+            f[0] = f[1] = f[2] = f[3] = 0.0f;
+            if (fill != nullptr) {
+                const float4 vf = reinterpret_cast<const float4*>(fill)[jc];
+                f[0] = vf.x, f[1] = vf.y, f[2] = vf.z, f[3] = vf.w;
             }
         } else {
-            for (int c = lane; c < rows * kt; c += 64) {
-                const int r = c / kt, p = c - r * kt;
-                u_out[(b0 + r) * kt + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a[i] = src_a[jc * 4 + i];
+                b[i] = src_b ? src_b[jc * 4 + i] : -1;
+                f[i] = fill ? fill[jc * 4 + i] : 0.0f;
             }
         }
-    }
-    // C1': the information bits packed (pl_count_errors_packed's reference), bits past kt cleared
-    if (ubits_out != nullptr)
-        for (int c = lane; c < rows * nq; c += 64) {
-            const int q = c % nq;
-            ubits_out[b0 * nq + c] = sw[c] & (q == nq - 1 ? last : 0xFFFFFFFFu);
+        const float* x4 = st + rl * epad;
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            // entries past E - 1 are clamped: a bad table reads another position, never another row
+            const int ia = a[i] < e_len ? a[i] : e_len - 1, ib = b[i] < e_len ? b[i] : e_len - 1;
+            v[i] = f[i];
+            if (ia >= 0) v[i] = ib >= 0 ? x4[ia] + x4[ib] : x4[ia];  // llr_1 + llr_3 (dec.py:629-633)
         }
+        float* o = llr_out + (L.b0 + r) * n + jc * 4;
+        if (tab_vec) {
+            *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = v[i];
+        }
+    }
+    wave_sync();
+}
+
+__global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
+    int64_t bs, int64_t row0, uint32_t k0, uint32_t k1, uint32_t it, float no, const uint32_t* __restrict__ frozen_words,
+    int n, int k, int kt, const uint32_t* __restrict__ g_rows, int degree, const int32_t* __restrict__ rm_idx, int e_len,
+    const int32_t* __restrict__ src_a, const int32_t* __restrict__ src_b, const float* __restrict__ fill,
+    float* __restrict__ u_out, uint32_t* __restrict__ ubits_out, float* __restrict__ llr_ch_out,
+    float* __restrict__ llr_out) {
+    __shared__ uint32_t s_g[kNrGWords];
+    __shared__ uint32_t lds[4 * 192];
+    __shared__ __attribute__((aligned(16))) float s_stage[4 * kNrStage];
+    __builtin_assume(n >= 32);  // whole words: wpc = n / 32, nb = 32
+    const WaveRows L = wave_rows(n, row0, bs);
+    const int nq = (kt + 31) / 32, nkq = (k + 31) / 32;  // words of the information bits / with the parity
+    uint32_t* sw = lds + L.wv * 192;                      // [cpw][nq] stream words
+    uint32_t* kw = sw + 64;                               // [cpw][nkq] information bits | parity
+    uint32_t* cwd = sw + 128;                             // [cpw][wpc] code words
+    float* st = s_stage + L.wv * kNrStage;
+    const int lane = L.lane, wpc = L.wpc, cpw = L.cpw, rows = L.rows;
+    const int64_t b0 = L.b0;
+
+    stage_crc_rows(s_g, g_rows, kt);
+    draw_stream_words(sw, nq, L, k0, k1, it);
+    __syncthreads();
+    crc_attach(kw, nkq, sw, nq, s_g, kt, degree, L);
+    wave_sync();
+    cwd[L.g * wpc + L.w] = encode_word(kw, nkq, frozen_words, L);
+    wave_sync();
+    if (rows <= 0) return;
+    store_u_rows(u_out, sw, nq, kt, L);
+    store_packed_rows(ubits_out, sw, nq, kt, L);
 
     const float scale = -2.8284271f / no;
     const Logit lc{scale * 0.70710677f, scale * sqrtf(no) * 0.70710677f * 1.17741002f};  // sqrt(2 ln 2)
@@ -390,29 +463,12 @@ __global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
     const int rpp = kNrStage / epad < cpw ? kNrStage / epad : cpw;  // rows per pass (>= 1: E <= kNrStage)
     const bool ch_vec = (e_len & 3) == 0 && ((reinterpret_cast<uintptr_t>(llr_ch_out) & 15) == 0) &&
                         ((reinterpret_cast<uintptr_t>(rm_idx) & 15) == 0);
-    const bool tab_vec = ((reinterpret_cast<uintptr_t>(src_a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(src_b) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(fill) & 15) == 0) && ((reinterpret_cast<uintptr_t>(llr_out) & 15) == 0);
-    const int nj = n >> 2, lnj = __builtin_ctz(nj);
     for (int r0 = 0; r0 < rows; r0 += rpp) {
         const int rc = rows - r0 < rpp ? rows - r0 : rpp;
         // C2: rate matching, QPSK, AWGN, demapper -> stage (+ llr_ch_out)
         for (int c = lane; c < rc * nch; c += 64) {
             const int rl = c / nch, ch = c - rl * nch, r = r0 + rl, p = ch * 4;
-            int id[4];
-            if (ch_vec) {
-                const int4 v = reinterpret_cast<const int4*>(rm_idx)[ch];
-                id[0] = v.x, id[1] = v.y, id[2] = v.z, id[3] = v.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) id[i] = p + i < e_len ? rm_idx[p + i] : 0;
-            }
-            const uint32_t* cw = cwd + r * wpc;
-            uint32_t bits = 0u;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int j = id[i] & (n - 1);  // a table entry outside the codeword cannot leave the row
-                bits |= ((cw[j >> 5] >> (j & 31)) & 1u) << i;
-            }
+            const uint32_t bits = gather_code_bits<4>(cwd + r * wpc, rm_idx, p, e_len, ch_vec, n);
             const U4 rnd = stream_block(k0, k1, row0 + b0 + r, it, 1, (uint32_t)ch);
             const float4 l = logits4(rnd, bits, lc);
             *reinterpret_cast<float4*>(st + rl * epad + p) = l;
@@ -428,55 +484,8 @@ __global__ __launch_bounds__(256) void nr_awgn_llr_kernel(
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // C3: rate recovery (pl_rate_recover's tables and arithmetic) from the stage
-        for (int c = lane; c < rc * nj; c += 64) {
-            const int rl = c >> lnj, jc = c & (nj - 1), r = r0 + rl;
-            int a[4], b[4];
-            float f[4];
-            if (tab_vec) {
-                const int4 va = reinterpret_cast<const int4*>(src_a)[jc];
-                a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
-                b[0] = b[1] = b[2] = b[3] = -1;
-                if (src_b != nullptr) {
-                    const int4 vb = reinterpret_cast<const int4*>(src_b)[jc];
-                    b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
-                }
-                f[0] = f[1] = f[2] = f[3] = 0.0f;
-                if (fill != nullptr) {
-                    const float4 vf = reinterpret_cast<const float4*>(fill)[jc];
-                    f[0] = vf.x, f[1] = vf.y, f[2] = vf.z, f[3] = vf.w;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    a[i] = src_a[jc * 4 + i];
-                    b[i] = src_b ? src_b[jc * 4 + i] : -1;
-                    f[i] = fill ? fill[jc * 4 + i] : 0.0f;
-                }
-            }
-            const float* x4 = st + rl * epad;
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                // entries past E - 1 are clamped: a bad table reads another position, never another row
-                const int ia = a[i] < e_len ? a[i] : e_len - 1, ib = b[i] < e_len ? b[i] : e_len - 1;
-                v[i] = f[i];
-                if (ia >= 0) v[i] = ib >= 0 ? x4[ia] + x4[ib] : x4[ia];  // llr_1 + llr_3 (dec.py:629-633)
-            }
-            float* o = llr_out + (b0 + r) * n + jc * 4;
-            if (tab_vec) {
-                *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = v[i];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
+        recover_rows(llr_out, st, epad, e_len, r0, rc, src_a, src_b, fill, n, L);
     }
 }
 
@@ -507,11 +516,17 @@ __device__ __forceinline__ float4 qam_receive(const U4& rnd, uint32_t bits, cons
         for (int j = 0; j < H; ++j) a |= ((bits >> ((ax >> 1) * M + 2 * j + (ax & 1))) & 1u) << (H - 1 - j);
         x[ax] = s_lev[a & ((1u << H) - 1u)];
     }
-    const float rs0 = rsig * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.x | 1u)));
-    const float rs1 = rsig * __builtin_amdgcn_sqrtf(32.0f - __builtin_amdgcn_logf((float)(rnd.z | 1u)));
-    const float t0 = __uint_as_float(0x3F800000u | (rnd.y >> 9)), t1 = __uint_as_float(0x3F800000u | (rnd.w >> 9));
-    return float4{__builtin_fmaf(rs0, __builtin_amdgcn_cosf(t0), x[0]), __builtin_fmaf(rs0, __builtin_amdgcn_sinf(t0), x[1]),
-                  __builtin_fmaf(rs1, __builtin_amdgcn_cosf(t1), x[2]), __builtin_fmaf(rs1, __builtin_amdgcn_sinf(t1), x[3])};
+    const Gauss4 g = box_muller(rnd, rsig);
+    return float4{__builtin_fmaf(g.rs0, g.c0, x[0]), __builtin_fmaf(g.rs0, g.s0, x[1]), __builtin_fmaf(g.rs1, g.c1, x[2]),
+                  __builtin_fmaf(g.rs1, g.s1, x[3])};
+}
+
+// The level table -> LDS (one thread; the caller's __syncthreads() follows)
+__device__ __forceinline__ void stage_levels(float* s_lev, const Qam& qam) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int a = 0; a < 16; ++a) s_lev[a] = qam.lev[a];
+    }
 }
 
 // Logits of the H bits of one axis from its received component y, written to out[0], out[2], ...
@@ -584,79 +599,21 @@ __global__ __launch_bounds__(256) void awgn_qam_llr_kernel(int64_t bs, int64_t r
                                                            float* __restrict__ y_out) {
     __shared__ uint32_t lds[4 * kWordsPerWave];
     __shared__ float s_lev[16];
-    const int wpc = n >= 32 ? n / 32 : 1, cpw = 64 / wpc, nb = n >= 32 ? 32 : n;
-    const int nq = (k + 31) / 32;  // stream words per row
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
-    uint32_t* sw = lds + wv * kWordsPerWave;                   // [cpw][nq] stream words
-    uint32_t* cwd = sw + cpw * nq;                             // [cpw][wpc] code words
-    const int g = lane / wpc, w = lane % wpc;
-    const int64_t row = row0 + b0 + g;
+    const WaveRows L = wave_rows(n, row0, bs);
+    const int nq = (k + 31) / 32;                 // stream words per row
+    uint32_t* sw = lds + L.wv * kWordsPerWave;    // [cpw][nq] stream words
+    uint32_t* cwd = sw + L.cpw * nq;              // [cpw][wpc] code words
+    const int lane = L.lane, wpc = L.wpc, rows = L.rows;
+    const int64_t b0 = L.b0;
 
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int a = 0; a < 16; ++a) s_lev[a] = qam.lev[a];
-    }
-    // A: stream words (rows past bs compute harmless values that are never stored)
-    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
+    stage_levels(s_lev, qam);
+    draw_stream_words(sw, nq, L, k0, k1, it);
     __syncthreads();
-
-    // B: information positions of this word (frozen bit 0), their first rank = information
-    // positions in the group's earlier words (prefix sum over the group's lanes)
-    const uint32_t live = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
-    const uint32_t info = ~frozen_words[w] & live;
-    int base = 0;
-    {
-        int c = __popc(info), incl = c;
-        for (int d = 1; d < wpc; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (w >= d) incl += o;
-        }
-        base = incl - c;
-    }
-    uint32_t x = 0u;
-    if (info) {
-        const uint32_t* srow = sw + g * nq;
-        const int q0 = base >> 5, sh = base & 31;
-        const uint32_t lo = srow[q0];
-        const uint32_t hi = q0 + 1 < nq ? srow[q0 + 1] : 0u;
-        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
-    }
-    for (int h = 1; h < nb; h <<= 1) x ^= (x >> h) & span_mask(h);  // x = u G_n (my_sn enc.py:85-96)
-    for (int hw = 1; hw < wpc; hw <<= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
-        if ((w & hw) == 0) x ^= other;
-    }
-    cwd[g * wpc + w] = x;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
+    cwd[L.g * wpc + L.w] = encode_word(sw, nq, frozen_words, L);
+    wave_sync();
     if (rows <= 0) return;
-    // C1: u rows (BinarySource output, float32 0/1)
-    if (u_out != nullptr && k > 0) {
-        if ((k & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
-            const int kq = k >> 2;
-            for (int c = lane; c < rows * kq; c += 64) {
-                const int r = c / kq, p = (c - r * kq) * 4;
-                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
-                reinterpret_cast<float4*>(u_out + (b0 + r) * k)[p >> 2] =
-                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
-            }
-        } else {
-            for (int c = lane; c < rows * k; c += 64) {
-                const int r = c / k, p = c - r * k;
-                u_out[(b0 + r) * k + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
-            }
-        }
-    }
-    // C1': the information bits packed (awgn_llr_kernel's layout), bits past k cleared
-    if (ubits_out != nullptr && k > 0) {
-        const uint32_t last = (k & 31) ? ((1u << (k & 31)) - 1u) : 0xFFFFFFFFu;
-        for (int r = 0; r < rows; ++r)
-            for (int q = lane; q < nq; q += 64) ubits_out[(b0 + r) * nq + q] = sw[r * nq + q] & (q == nq - 1 ? last : 0xFFFFFFFFu);
-    }
+    store_u_rows(u_out, sw, nq, k, L);
+    store_packed_rows(ubits_out, sw, nq, k, L);
     // C2: y = x + sqrt(no) * N(0, 1/2) per component (awgn.py:24-29, utils.py:11-15), the demapper.
     // Pair pc of a row = positions [2M pc, 2M pc + 2M) (n >= 2M: inside one code word, M = 4, 8),
     // noise block pc; with one symbol per row (n = M) the pair's second half is unused.
@@ -708,133 +665,40 @@ __global__ __launch_bounds__(256) void nr_awgn_qam_llr_kernel(
     __shared__ uint32_t lds[4 * 192];
     __shared__ __attribute__((aligned(16))) float s_stage[4 * kNrStage];
     __shared__ float s_lev[16];
-    const int wpc = n / 32, cpw = 64 / wpc;
+    __builtin_assume(n >= 32);  // whole words: wpc = n / 32, nb = 32
+    const WaveRows L = wave_rows(n, row0, bs);
     const int nq = (kt + 31) / 32, nkq = (k + 31) / 32;  // words of the information bits / with the parity
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t b0 = ((int64_t)blockIdx.x * 4 + wv) * cpw;  // first row of this wave
-    uint32_t* sw = lds + wv * 192;                             // [cpw][nq] stream words
-    uint32_t* kw = sw + 64;                                    // [cpw][nkq] information bits | parity
-    uint32_t* cwd = sw + 128;                                  // [cpw][wpc] code words
-    float* st = s_stage + wv * kNrStage;
-    const int g = lane / wpc, w = lane % wpc;
-    const int64_t row = row0 + b0 + g;
+    uint32_t* sw = lds + L.wv * 192;                      // [cpw][nq] stream words
+    uint32_t* kw = sw + 64;                               // [cpw][nkq] information bits | parity
+    uint32_t* cwd = sw + 128;                             // [cpw][wpc] code words
+    float* st = s_stage + L.wv * kNrStage;
+    const int lane = L.lane, wpc = L.wpc, cpw = L.cpw, rows = L.rows;
+    const int64_t b0 = L.b0;
 
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int a = 0; a < 16; ++a) s_lev[a] = qam.lev[a];
-    }
-    for (int m = threadIdx.x; m < kt; m += 256) s_g[m + (m >> 5)] = g_rows[m];
-    // A: stream words (rows past bs compute harmless values that are never stored)
-    for (int q = w; q < nq; q += wpc) sw[g * nq + q] = comp(stream_block(k0, k1, row, it, 0, q >> 2), q & 3);
+    stage_levels(s_lev, qam);
+    stage_crc_rows(s_g, g_rows, kt);
+    draw_stream_words(sw, nq, L, k0, k1, it);
     __syncthreads();
-
-    // A': parity of the row; nq <= wpc (kt < n), so lane w < nq owns word w of its row
-    const uint32_t last = (kt & 31) ? ((1u << (kt & 31)) - 1u) : 0xFFFFFFFFu;
-    const uint32_t mine = w < nq ? sw[g * nq + w] & (w == nq - 1 ? last : 0xFFFFFFFFu) : 0u;
-    uint32_t par = 0u;
-    {
-        const uint32_t* gr = s_g + w * 33;
-#pragma unroll 8
-        for (int j = 0; j < 32; ++j)
-            if ((mine >> j) & 1u) par ^= gr[j];
-    }
-    for (int d = 1; d < wpc; d <<= 1) par ^= (uint32_t)__shfl_xor((int)par, d, 64);
-    if (degree < 32) par &= (1u << degree) - 1u;
-    if (w < nkq) {
-        const uint64_t pv = (uint64_t)par << (kt & 31);  // parity bit c = bit kt + c of the row
-        const int pw = kt >> 5;
-        kw[g * nkq + w] = mine | (w == pw ? (uint32_t)pv : 0u) | (w == pw + 1 ? (uint32_t)(pv >> 32) : 0u);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    // B: the k bits deposited at the information positions, XOR butterfly (awgn_llr_kernel's B)
-    const uint32_t info = ~frozen_words[w];
-    int base = 0;
-    {
-        int c = __popc(info), incl = c;
-        for (int d = 1; d < wpc; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (w >= d) incl += o;
-        }
-        base = incl - c;
-    }
-    uint32_t x = 0u;
-    if (info) {
-        const uint32_t* srow = kw + g * nkq;
-        const int q0 = base >> 5, sh = base & 31;
-        const uint32_t lo = q0 < nkq ? srow[q0] : 0u;
-        const uint32_t hi = q0 + 1 < nkq ? srow[q0 + 1] : 0u;
-        x = expand_bits((uint32_t)((((uint64_t)hi << 32) | lo) >> sh), info);
-    }
-    for (int h = 1; h < 32; h <<= 1) x ^= (x >> h) & span_mask(h);
-    for (int hw = 1; hw < wpc; hw <<= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
-        if ((w & hw) == 0) x ^= other;
-    }
-    cwd[g * wpc + w] = x;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    const int rows = bs - b0 < cpw ? (int)(bs - b0) : cpw;  // rows of this wave to store
+    crc_attach(kw, nkq, sw, nq, s_g, kt, degree, L);
+    wave_sync();
+    cwd[L.g * wpc + L.w] = encode_word(kw, nkq, frozen_words, L);
+    wave_sync();
     if (rows <= 0) return;
-    // C1: u rows (BinarySource output, float32 0/1)
-    if (u_out != nullptr && kt > 0) {
-        if ((kt & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_out) & 15) == 0)) {
-            const int kq = kt >> 2;
-            for (int c = lane; c < rows * kq; c += 64) {
-                const int r = c / kq, p = (c - r * kq) * 4;
-                const uint32_t v = sw[r * nq + (p >> 5)] >> (p & 31);
-                reinterpret_cast<float4*>(u_out + (b0 + r) * kt)[p >> 2] =
-                    float4{(float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u)};
-            }
-        } else {
-            for (int c = lane; c < rows * kt; c += 64) {
-                const int r = c / kt, p = c - r * kt;
-                u_out[(b0 + r) * kt + p] = (float)((sw[r * nq + (p >> 5)] >> (p & 31)) & 1u);
-            }
-        }
-    }
-    // C1': the information bits packed (pl_count_errors_packed's reference), bits past kt cleared
-    if (ubits_out != nullptr)
-        for (int c = lane; c < rows * nq; c += 64) {
-            const int q = c % nq;
-            ubits_out[b0 * nq + c] = sw[c] & (q == nq - 1 ? last : 0xFFFFFFFFu);
-        }
+    store_u_rows(u_out, sw, nq, kt, L);
+    store_packed_rows(ubits_out, sw, nq, kt, L);
 
     const float inv_no = 1.0f / no, rsig = sqrtf(no) * 0.70710677f * 1.17741002f;  // sqrt(2 ln 2)
     const int ns = e_len / M, npair = (ns + 1) >> 1;  // symbols and symbol pairs per row
     const int epad = ((e_len + 3) >> 2) * 4;
     const int rpp = kNrStage / epad < cpw ? kNrStage / epad : cpw;  // rows per pass (>= 1: E <= kNrStage)
     const bool idx_vec = (reinterpret_cast<uintptr_t>(rm_idx) & 15) == 0;
-    const bool tab_vec = ((reinterpret_cast<uintptr_t>(src_a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(src_b) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(fill) & 15) == 0) && ((reinterpret_cast<uintptr_t>(llr_out) & 15) == 0);
-    const int nj = n >> 2, lnj = __builtin_ctz(nj);
     for (int r0 = 0; r0 < rows; r0 += rpp) {
         const int rc = rows - r0 < rpp ? rows - r0 : rpp;
         // C2: rate matching, QAM, AWGN, demapper -> stage (+ llr_ch_out, y_out)
         for (int c = lane; c < rc * npair; c += 64) {
             const int rl = c / npair, pc = c - rl * npair, r = r0 + rl, p = pc * 2 * M;
-            int id[2 * M];
-            if (idx_vec && p + 2 * M <= e_len) {
-#pragma unroll
-                for (int i = 0; i < 2 * M; i += 4) {
-                    const int4 v = *reinterpret_cast<const int4*>(rm_idx + p + i);
-                    id[i] = v.x, id[i + 1] = v.y, id[i + 2] = v.z, id[i + 3] = v.w;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 2 * M; ++i) id[i] = p + i < e_len ? rm_idx[p + i] : 0;
-            }
-            const uint32_t* cw = cwd + r * wpc;
-            uint32_t bits = 0u;
-#pragma unroll
-            for (int i = 0; i < 2 * M; ++i) {
-                const int j = id[i] & (n - 1);  // a table entry outside the codeword cannot leave the row
-                bits |= ((cw[j >> 5] >> (j & 31)) & 1u) << i;
-            }
+            const uint32_t bits =
+                gather_code_bits<2 * M>(cwd + r * wpc, rm_idx, p, e_len, idx_vec && p + 2 * M <= e_len, n);
             const U4 rnd = stream_block(k0, k1, row0 + b0 + r, it, 1, (uint32_t)pc);
             const float4 y = qam_receive<M>(rnd, bits, s_lev, rsig);
 #pragma unroll 1
@@ -859,59 +723,30 @@ __global__ __launch_bounds__(256) void nr_awgn_qam_llr_kernel(
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // C3: rate recovery (pl_rate_recover's tables and arithmetic) from the stage
-        for (int c = lane; c < rc * nj; c += 64) {
-            const int rl = c >> lnj, jc = c & (nj - 1), r = r0 + rl;
-            int a[4], b[4];
-            float f[4];
-            if (tab_vec) {
-                const int4 va = reinterpret_cast<const int4*>(src_a)[jc];
-                a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
-                b[0] = b[1] = b[2] = b[3] = -1;
-                if (src_b != nullptr) {
-                    const int4 vb = reinterpret_cast<const int4*>(src_b)[jc];
-                    b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
-                }
-                f[0] = f[1] = f[2] = f[3] = 0.0f;
-                if (fill != nullptr) {
-                    const float4 vf = reinterpret_cast<const float4*>(fill)[jc];
-                    f[0] = vf.x, f[1] = vf.y, f[2] = vf.z, f[3] = vf.w;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    a[i] = src_a[jc * 4 + i];
-                    b[i] = src_b ? src_b[jc * 4 + i] : -1;
-                    f[i] = fill ? fill[jc * 4 + i] : 0.0f;
-                }
-            }
-            const float* x4 = st + rl * epad;
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                // entries past E - 1 are clamped: a bad table reads another position, never another row
-                const int ia = a[i] < e_len ? a[i] : e_len - 1, ib = b[i] < e_len ? b[i] : e_len - 1;
-                v[i] = f[i];
-                if (ia >= 0) v[i] = ib >= 0 ? x4[ia] + x4[ib] : x4[ia];  // llr_1 + llr_3 (dec.py:629-633)
-            }
-            float* o = llr_out + (b0 + r) * n + jc * 4;
-            if (tab_vec) {
-                *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = v[i];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
+        recover_rows(llr_out, st, epad, e_len, r0, rc, src_a, src_b, fill, n, L);
     }
 }
 
 constexpr int kRowsPerWave = 8;  // rows a wave of the counting kernels takes
+
+// counts[0..1] += the block's sum of each wave's (be, ke), the wave's totals in its lane 0: the
+// block reduces in LDS, one pair of 64-bit atomics per block, none for a zero.  Block-wide.
+__device__ __forceinline__ void block_add_pair(unsigned long long be, unsigned long long ke, int lane, int wv,
+                                               unsigned long long* __restrict__ counts) {
+    __shared__ unsigned long long part[4][2];
+    if (lane == 0) {
+        part[wv][0] = be;
+        part[wv][1] = ke;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long b = part[0][0] + part[1][0] + part[2][0] + part[3][0];
+        const unsigned long long e = part[0][1] + part[1][1] + part[2][1] + part[3][1];
+        if (b) atomicAdd(&counts[0], b);
+        if (e) atomicAdd(&counts[1], e);
+    }
+}
 
 // Bit and block errors of the first k_cmp columns of [rows, row_len] decided bits (fp32 0/1 or
 // bytes) against packed reference bits ([rows, ceil(k_cmp/32)] words, bit m % 32 of word m / 32):
@@ -920,7 +755,6 @@ template <typename T>
 __global__ __launch_bounds__(256) void count_errors_packed_kernel(const T* __restrict__ bits, int64_t rows, int row_len,
                                                                   int k_cmp, const uint32_t* __restrict__ ref,
                                                                   unsigned long long* __restrict__ counts) {
-    __shared__ unsigned long long part[4][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * kRowsPerWave;
     const int nq = (k_cmp + 31) / 32;
@@ -937,17 +771,7 @@ __global__ __launch_bounds__(256) void count_errors_packed_kernel(const T* __res
         blk_err += __builtin_amdgcn_ballot_w64(e != 0) != 0 ? 1u : 0u;
     }
     for (int off = 32; off >= 1; off >>= 1) bit_err += __shfl_xor(bit_err, off, 64);
-    if (lane == 0) {
-        part[wv][0] = bit_err;
-        part[wv][1] = blk_err;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long be = part[0][0] + part[1][0] + part[2][0] + part[3][0];
-        const unsigned long long ke = part[0][1] + part[1][1] + part[2][1] + part[3][1];
-        if (be) atomicAdd(&counts[0], be);
-        if (ke) atomicAdd(&counts[1], ke);
-    }
+    block_add_pair(bit_err, blk_err, lane, wv, counts);
 }
 
 // Bit and block errors of a [rows, k] pair of 0/1 float tensors (exact comparisons, as
@@ -955,7 +779,6 @@ __global__ __launch_bounds__(256) void count_errors_packed_kernel(const T* __res
 // rows are 16-byte aligned), the block reduces in LDS, one pair of 64-bit atomics per block.
 __global__ __launch_bounds__(256) void count_errors_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            int64_t rows, int k, unsigned long long* __restrict__ counts) {
-    __shared__ unsigned long long part[4][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t r0 = ((int64_t)blockIdx.x * 4 + wv) * kRowsPerWave;
     uint32_t bit_err = 0, blk_err = 0;
@@ -989,17 +812,7 @@ __global__ __launch_bounds__(256) void count_errors_kernel(const float* __restri
         }
     }
     for (int off = 32; off >= 1; off >>= 1) bit_err += __shfl_xor(bit_err, off, 64);
-    if (lane == 0) {
-        part[wv][0] = bit_err;
-        part[wv][1] = blk_err;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long be = part[0][0] + part[1][0] + part[2][0] + part[3][0];
-        const unsigned long long ke = part[0][1] + part[1][1] + part[2][1] + part[3][1];
-        if (be) atomicAdd(&counts[0], be);
-        if (ke) atomicAdd(&counts[1], ke);
-    }
+    block_add_pair(bit_err, blk_err, lane, wv, counts);
 }
 
 // counts[0..1] += sums of the [bit, block] error pairs the decode+count kernel stored per wave:
@@ -1008,7 +821,6 @@ constexpr int kSumBlocks = 64;
 
 __global__ __launch_bounds__(256) void sum_pairs_kernel(const int32_t* __restrict__ part, int64_t pairs,
                                                         unsigned long long* __restrict__ counts) {
-    __shared__ unsigned long long red[4][2];
     unsigned long long be = 0, ke = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pairs; i += (int64_t)gridDim.x * 256) {
         be += (uint32_t)part[2 * i];
@@ -1018,18 +830,7 @@ __global__ __launch_bounds__(256) void sum_pairs_kernel(const int32_t* __restric
         be += __shfl_xor(be, off, 64);
         ke += __shfl_xor(ke, off, 64);
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[wv][0] = be;
-        red[wv][1] = ke;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long b = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        const unsigned long long e = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-        if (b) atomicAdd(&counts[0], b);
-        if (e) atomicAdd(&counts[1], e);
-    }
+    block_add_pair(be, ke, threadIdx.x & 63, threadIdx.x >> 6, counts);
 }
 
 }  // namespace
@@ -1047,24 +848,63 @@ int launch_sum_pairs(const int32_t* part, int64_t pairs, int64_t* counts, hipStr
 
 extern "C" {
 
-static int awgn_launch(const pl_plan* p, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no,
-                       float* u_out, uint32_t* ubits_out, float* llr_out, void* stream, const char* what) {
-    if (!p || bs < 0 || row0 < 0 || (bs > 0 && !llr_out) || !(no > 0.0f) || (iteration >> 32) != 0) {
-        pl::set_error(std::string(what) + ": bad arguments (no must be > 0, iteration < 2^32)");
-        return PL_EINVAL;
-    }
-    if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
-    if (bs == 0) return PL_OK;
-    const int wpc = p->n >= 32 ? p->n / 32 : 1;
-    const int64_t cpw = 64 / wpc;
+static int einval(const std::string& msg) {
+    pl::set_error(msg);
+    return PL_EINVAL;
+}
+
+// The argument check of the two QPSK entry points (one message for all of it)
+static int qpsk_checks(const char* what, const pl_plan* p, int64_t bs, int64_t row0, float no, uint64_t iteration,
+                       const float* llr_out) {
+    if (!p || bs < 0 || row0 < 0 || (bs > 0 && !llr_out) || !(no > 0.0f) || (iteration >> 32) != 0)
+        return einval(std::string(what) + ": bad arguments (no must be > 0, iteration < 2^32)");
+    return PL_OK;
+}
+
+// The checks of the two NR entry points on the mother code, in the order they report: the code
+// length, k, the caller's complaint about E (pl_nr_awgn_qpsk_llr's place for it; empty: none), the
+// tables.
+static int nr_checks(const char* what, const pl_plan* p, int32_t k_target, int32_t crc_degree, const std::string& e_error,
+                     int64_t bs, const uint32_t* g_rows, const int32_t* rm_idx, const int32_t* src_a) {
+    const std::string w(what);
+    if (p->n < 32 || p->n > 1024) return einval(w + ": the mother code length must be 32 ... 1024");
+    if (k_target < 0 || crc_degree < 1 || crc_degree > 32 || p->k != k_target + crc_degree)
+        return einval(w + ": the plan's k must equal k_target + crc_degree (crc_degree 1 ... 32)");
+    if (!e_error.empty()) return einval(w + e_error);
+    if (bs > 0 && (!rm_idx || !src_a || (k_target > 0 && !g_rows)))
+        return einval(w + ": g_rows, rm_idx and src_a must be given");
+    return PL_OK;
+}
+
+// Blocks (4 waves of 64 / max(1, n / 32) rows) of a producer launch over bs > 0 rows; 0, and the
+// error set, where one launch cannot hold them.
+static unsigned producer_blocks(const char* what, int n, int64_t bs) {
+    const int64_t cpw = 64 / (n >= 32 ? n / 32 : 1);
     const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
     if (blocks > 0x7fffffffLL) {
         pl::set_error(std::string(what) + ": batch too large for one launch");
-        return PL_EINVAL;
+        return 0;
     }
-    hipLaunchKernelGGL(awgn_llr_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs,
-                       row0, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n,
-                       p->k, u_out, llr_out, ubits_out);
+    return (unsigned)blocks;
+}
+
+static Qam make_qam(int m) {
+    Qam q;
+    pl::qam_levels(m, q.lev, &q.d);
+    q.inv2d = 1.0f / (2.0f * q.d);
+    return q;
+}
+
+static int awgn_launch(const pl_plan* p, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no,
+                       float* u_out, uint32_t* ubits_out, float* llr_out, void* stream, const char* what) {
+    if (int r = qpsk_checks(what, p, bs, row0, no, iteration, llr_out)) return r;
+    if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
+    if (bs == 0) return PL_OK;
+    const unsigned blocks = producer_blocks(what, p->n, bs);
+    if (!blocks) return PL_EINVAL;
+    hipLaunchKernelGGL(awgn_llr_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k,
+                       u_out, llr_out, ubits_out);
     return pl::check_hip(hipGetLastError(), what);
 }
 
@@ -1084,38 +924,17 @@ int pl_nr_awgn_qpsk_llr(const pl_plan* p, int32_t k_target, const uint32_t* g_ro
                         uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no, uint32_t* ubits_out,
                         float* u_out, float* llr_ch_out, float* llr_out, void* stream) {
     const char* what = "pl_nr_awgn_qpsk_llr";
-    if (!p || bs < 0 || row0 < 0 || (bs > 0 && !llr_out) || !(no > 0.0f) || (iteration >> 32) != 0) {
-        pl::set_error(std::string(what) + ": bad arguments (no must be > 0, iteration < 2^32)");
-        return PL_EINVAL;
-    }
-    if (p->n < 32 || p->n > 1024) {
-        pl::set_error(std::string(what) + ": the mother code length must be 32 ... 1024");
-        return PL_EINVAL;
-    }
-    if (k_target < 0 || crc_degree < 1 || crc_degree > 32 || p->k != k_target + crc_degree) {
-        pl::set_error(std::string(what) + ": the plan's k must equal k_target + crc_degree (crc_degree 1 ... 32)");
-        return PL_EINVAL;
-    }
-    if (e < 2 || (e & 1) || e > kNrStage) {
-        pl::set_error(std::string(what) + ": E must be even (whole QPSK symbols), 2 ... " + std::to_string(kNrStage));
-        return PL_EINVAL;
-    }
-    if (bs > 0 && (!rm_idx || !src_a || (k_target > 0 && !g_rows))) {
-        pl::set_error(std::string(what) + ": g_rows, rm_idx and src_a must be given");
-        return PL_EINVAL;
-    }
+    if (int r = qpsk_checks(what, p, bs, row0, no, iteration, llr_out)) return r;
+    const std::string e_error = e < 2 || (e & 1) || e > kNrStage
+        ? ": E must be even (whole QPSK symbols), 2 ... " + std::to_string(kNrStage) : "";
+    if (int r = nr_checks(what, p, k_target, crc_degree, e_error, bs, g_rows, rm_idx, src_a)) return r;
     if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
     if (bs == 0) return PL_OK;
-    const int64_t cpw = 64 / (p->n / 32);
-    const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
-    if (blocks > 0x7fffffffLL) {
-        pl::set_error(std::string(what) + ": batch too large for one launch");
-        return PL_EINVAL;
-    }
-    hipLaunchKernelGGL(nr_awgn_llr_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs,
-                       row0, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n,
-                       p->k, k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, u_out, ubits_out, llr_ch_out,
-                       llr_out);
+    const unsigned blocks = producer_blocks(what, p->n, bs);
+    if (!blocks) return PL_EINVAL;
+    hipLaunchKernelGGL(nr_awgn_llr_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k,
+                       k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, u_out, ubits_out, llr_ch_out, llr_out);
     return pl::check_hip(hipGetLastError(), what);
 }
 
@@ -1124,30 +943,14 @@ int pl_nr_awgn_qpsk_llr(const pl_plan* p, int32_t k_target, const uint32_t* g_ro
 static int qam_common_checks(const char* what, int32_t m, int64_t bs, int64_t row0, float no, uint64_t iteration,
                              const float* y_out, const float* llr_out) {
     const std::string w(what);
-    if (m != 2 && m != 4 && m != 6 && m != 8) {
-        pl::set_error(w + ": bits_per_symbol must be 2, 4, 6 or 8, got " + std::to_string(m));
-        return PL_EINVAL;
-    }
-    if (m == 2 && y_out) {
-        pl::set_error(w + ": y_out must be NULL with bits_per_symbol 2 (the QPSK kernels do not write it)");
-        return PL_EINVAL;
-    }
-    if (bs < 0 || row0 < 0) {
-        pl::set_error(w + ": bs and row0 must be >= 0");
-        return PL_EINVAL;
-    }
-    if (!(no > 0.0f)) {
-        pl::set_error(w + ": no must be > 0");
-        return PL_EINVAL;
-    }
-    if ((iteration >> 32) != 0) {
-        pl::set_error(w + ": iteration must be < 2^32");
-        return PL_EINVAL;
-    }
-    if (bs > 0 && !llr_out) {
-        pl::set_error(w + ": llr_out must be given");
-        return PL_EINVAL;
-    }
+    if (m != 2 && m != 4 && m != 6 && m != 8)
+        return einval(w + ": bits_per_symbol must be 2, 4, 6 or 8, got " + std::to_string(m));
+    if (m == 2 && y_out)
+        return einval(w + ": y_out must be NULL with bits_per_symbol 2 (the QPSK kernels do not write it)");
+    if (bs < 0 || row0 < 0) return einval(w + ": bs and row0 must be >= 0");
+    if (!(no > 0.0f)) return einval(w + ": no must be > 0");
+    if ((iteration >> 32) != 0) return einval(w + ": iteration must be < 2^32");
+    if (bs > 0 && !llr_out) return einval(w + ": llr_out must be given");
     return PL_OK;
 }
 
@@ -1156,32 +959,19 @@ int pl_awgn_qam_llr(const pl_plan* p, int32_t bits_per_symbol, uint64_t seed, ui
     const char* what = "pl_awgn_qam_llr";
     const int m = bits_per_symbol;
     if (int r = qam_common_checks(what, m, bs, row0, no, iteration, y_out, llr_out)) return r;
-    if (!p) {
-        pl::set_error(std::string(what) + ": plan must be given");
-        return PL_EINVAL;
-    }
+    if (!p) return einval(std::string(what) + ": plan must be given");
     if (m == 2) return awgn_launch(p, seed, iteration, row0, bs, no, u_out, ubits_out, llr_out, stream, what);
-    if (p->n % m != 0 || p->n > 2048) {
-        pl::set_error(std::string(what) + ": bits_per_symbol " + std::to_string(m) + " must divide the code length n = " +
+    if (p->n % m != 0 || p->n > 2048)
+        return einval(std::string(what) + ": bits_per_symbol " + std::to_string(m) + " must divide the code length n = " +
                       std::to_string(p->n) + " (n <= 2048)");
-        return PL_EINVAL;
-    }
     if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
     if (bs == 0) return PL_OK;
-    const int wpc = p->n >= 32 ? p->n / 32 : 1;
-    const int64_t cpw = 64 / wpc;
-    const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
-    if (blocks > 0x7fffffffLL) {
-        pl::set_error(std::string(what) + ": batch too large for one launch");
-        return PL_EINVAL;
-    }
-    Qam q;
-    pl::qam_levels(m, q.lev, &q.d);
-    q.inv2d = 1.0f / (2.0f * q.d);
+    const unsigned blocks = producer_blocks(what, p->n, bs);
+    if (!blocks) return PL_EINVAL;
     auto* kern = m == 4 ? awgn_qam_llr_kernel<4> : awgn_qam_llr_kernel<8>;  // 6 never divides a power of two
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k, q,
-                       u_out, llr_out, ubits_out, y_out);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k, make_qam(m), u_out,
+                       llr_out, ubits_out, y_out);
     return pl::check_hip(hipGetLastError(), what);
 }
 
@@ -1195,44 +985,21 @@ int pl_nr_awgn_qam_llr(const pl_plan* p, int32_t bits_per_symbol, int32_t k_targ
     if (m == 2)
         return pl_nr_awgn_qpsk_llr(p, k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, seed, iteration, row0, bs,
                                    no, ubits_out, u_out, llr_ch_out, llr_out, stream);
-    if (e < m || e % m != 0 || e > kNrStage) {
-        pl::set_error(std::string(what) + ": E must be a multiple of bits_per_symbol " + std::to_string(m) +
+    if (e < m || e % m != 0 || e > kNrStage)
+        return einval(std::string(what) + ": E must be a multiple of bits_per_symbol " + std::to_string(m) +
                       " (whole symbols), " + std::to_string(m) + " ... " + std::to_string(kNrStage) + ", got " +
                       std::to_string(e));
-        return PL_EINVAL;
-    }
-    if (!p) {
-        pl::set_error(std::string(what) + ": plan must be given");
-        return PL_EINVAL;
-    }
-    if (p->n < 32 || p->n > 1024) {
-        pl::set_error(std::string(what) + ": the mother code length must be 32 ... 1024");
-        return PL_EINVAL;
-    }
-    if (k_target < 0 || crc_degree < 1 || crc_degree > 32 || p->k != k_target + crc_degree) {
-        pl::set_error(std::string(what) + ": the plan's k must equal k_target + crc_degree (crc_degree 1 ... 32)");
-        return PL_EINVAL;
-    }
-    if (bs > 0 && (!rm_idx || !src_a || (k_target > 0 && !g_rows))) {
-        pl::set_error(std::string(what) + ": g_rows, rm_idx and src_a must be given");
-        return PL_EINVAL;
-    }
+    if (!p) return einval(std::string(what) + ": plan must be given");
+    if (int r = nr_checks(what, p, k_target, crc_degree, "", bs, g_rows, rm_idx, src_a)) return r;
     if (int r = pl::check_device(p, static_cast<hipStream_t>(stream), what)) return r;
     if (bs == 0) return PL_OK;
-    const int64_t cpw = 64 / (p->n / 32);
-    const int64_t blocks = ((bs + cpw - 1) / cpw + 3) / 4;
-    if (blocks > 0x7fffffffLL) {
-        pl::set_error(std::string(what) + ": batch too large for one launch");
-        return PL_EINVAL;
-    }
-    Qam q;
-    pl::qam_levels(m, q.lev, &q.d);
-    q.inv2d = 1.0f / (2.0f * q.d);
+    const unsigned blocks = producer_blocks(what, p->n, bs);
+    if (!blocks) return PL_EINVAL;
     auto* kern = m == 4 ? nr_awgn_qam_llr_kernel<4> : m == 6 ? nr_awgn_qam_llr_kernel<6> : nr_awgn_qam_llr_kernel<8>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0,
-                       (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k,
-                       k_target, g_rows, crc_degree, rm_idx, e, src_a, src_b, fill, q, u_out, ubits_out, llr_ch_out,
-                       llr_out, y_out);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), bs, row0, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), (uint32_t)iteration, no, p->d_frozen_words, p->n, p->k, k_target, g_rows,
+                       crc_degree, rm_idx, e, src_a, src_b, fill, make_qam(m), u_out, ubits_out, llr_ch_out, llr_out,
+                       y_out);
     return pl::check_hip(hipGetLastError(), what);
 }
 

@@ -9,20 +9,10 @@
 #include <stdint.h>
 
 #include "../../../include/polar_mi355x.h"
+#include "butterfly.h"
 #include "plan.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t span_mask(int h) {
-    // positions whose index bit log2(h) is 0 (the "upper" element of each butterfly)
-    switch (h) {
-        case 1: return 0x55555555u;
-        case 2: return 0x33333333u;
-        case 4: return 0x0f0f0f0fu;
-        case 8: return 0x00ff00ffu;
-        default: return 0x0000ffffu;  // 16
-    }
-}
 
 __global__ __launch_bounds__(256) void encode_kernel(const float* __restrict__ u, int64_t bs, float* __restrict__ cw,
                                                      const int32_t* __restrict__ info_rank, int n, int k) {
@@ -42,11 +32,7 @@ __global__ __launch_bounds__(256) void encode_kernel(const float* __restrict__ u
             if (r >= 0 && ur[r] != 0.0f) x |= 1u << b;
         }
     }
-    for (int h = 1; h < nb; h <<= 1) x ^= (x >> h) & span_mask(h);
-    for (int hw = 1; hw < wpc; hw <<= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)x, hw, 64);
-        if ((w & hw) == 0) x ^= other;
-    }
+    x = pl::polar_butterfly(x, nb, wpc, w);
     if (valid) {
         float* o = cw + row * n + w * 32;
         for (int b = 0; b < nb; ++b) o[b] = ((x >> b) & 1u) ? 1.0f : 0.0f;

@@ -6,10 +6,14 @@
     encoder and Gray mapping exact);
   * logits have the reference demapper's distribution at 2 dB (mean (2/no)(2c-1), variance 4/no);
   * SC BLER through FusedAWGN matches the reference's measured BLER table within binomial bounds;
-  * pl_count_errors equals the reference's count_errors / count_block_errors exactly.
+  * pl_count_errors equals the reference's count_errors / count_block_errors exactly;
+  * every producer entry point writes the same values through its scalar store paths (float outputs
+    4 bytes past 16-byte alignment) as through its vector paths.
 The reference draws from torch's CPU generator, which no GPU stream reproduces: parity of the
 producer is statistical by construction (the CPU-device System_AWGN_model keeps the bit-exact path).
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -107,3 +111,102 @@ def test_sim_ber_with_fused_model(pa):
                                  device="cuda", return_counts=True)
     assert (cnt[:, 3] % 4000 == 0).all() and cnt[0, 1] >= 500
     assert bler[0] > bler[1] > bler[2] > 0
+
+
+# ---- the scalar store paths ---------------------------------------------------------------------
+# The producers store 16 bytes at a time where a row layout and the output pointer allow it, and
+# element by element otherwise: C1 with k % 4 != 0 or a misaligned u_out, C2 / C3 with a misaligned
+# llr_out, the NR kernels' ch_vec == false path.  Each entry point runs twice on the same
+# (seed, iteration, row0): float outputs at the start of a fresh tensor, then one float into a tensor
+# one float longer -- a valid, in-bounds pointer 4 bytes past 16-byte alignment.  Every value must be
+# the same, and the float in front of a shifted output must stay untouched.
+A_SEED, A_IT, A_ROW0, A_NO = 7, 3, 3, 0.5
+
+
+def _floats(numel, off):
+    """(whole tensor, the numel floats starting `off` floats in) of a fresh NaN-filled tensor."""
+    t = torch.full((numel + off,), float("nan"), device="cuda")
+    assert t.data_ptr() % 16 == 0 and t[off:].data_ptr() % 16 == 4 * off
+    return t, t[off:]
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _aligned_equals_shifted(run):
+    """run(off) -> ({name: _floats(...)}, [other outputs]); off = 0 against off = 1."""
+    fa, oa = run(0)
+    fb, ob = run(1)
+    torch.cuda.synchronize()
+    for name in fa:
+        assert not torch.isnan(fa[name][1]).any(), name  # every element written
+        assert torch.equal(fa[name][1], fb[name][1]), name
+        assert torch.isnan(fb[name][0][0]), name  # nothing written in front of the pointer
+    for x, y in zip(oa, ob):
+        assert torch.equal(x, y)
+
+
+@pytest.mark.parametrize("k,n,bs", [(11, 16, 37), (128, 256, 37), (512, 1024, 5)])
+def test_qpsk_scalar_store_paths_match_the_vector_paths(pa, k, n, bs):
+    """(11, 16): n < 32 and k % 4 != 0; (128, 256) x 37: a ragged last wave; (512, 1024) x 5: the
+    rows-outer path (nch >= 64) against its scalar twin."""
+    from polar_amd import _lib
+    fp = pa.reference_frozen_pos(k, n).numpy() if n > 16 else np.sort(np.random.default_rng(n + k).permutation(n)[: n - k])
+    plan = _plan(pa, fp, n)
+    L, st = _lib.lib(), _lib.current_stream_ptr(plan.device)
+
+    def run(off):
+        f = {"u": _floats(bs * k, off), "llr": _floats(bs * n, off), "llr_bits": _floats(bs * n, off)}
+        ubits = torch.zeros((bs, (k + 31) // 32), dtype=torch.int32, device="cuda")
+        _lib.check(L.pl_awgn_qpsk_llr(plan.handle, A_SEED, A_IT, A_ROW0, bs, A_NO, _p(f["u"][1]), _p(f["llr"][1]), st),
+                   "pl_awgn_qpsk_llr")
+        _lib.check(L.pl_awgn_qpsk_llr_bits(plan.handle, A_SEED, A_IT, A_ROW0, bs, A_NO, _p(ubits), _p(f["llr_bits"][1]),
+                                           st), "pl_awgn_qpsk_llr_bits")
+        return f, [ubits]
+    _aligned_equals_shifted(run)
+
+
+@pytest.mark.parametrize("n,m", [(32, 8), (64, 4)])
+def test_qam_scalar_store_paths_match_the_vector_paths(pa, n, m):
+    from polar_amd import _lib
+    k, bs = n // 2, 37
+    plan = _plan(pa, pa.reference_frozen_pos(k, n).numpy(), n)
+    L, st = _lib.lib(), _lib.current_stream_ptr(plan.device)
+
+    def run(off):
+        f = {"u": _floats(bs * k, off), "y": _floats(bs * (n // m) * 2, off), "llr": _floats(bs * n, off)}
+        ubits = torch.zeros((bs, (k + 31) // 32), dtype=torch.int32, device="cuda")
+        _lib.check(L.pl_awgn_qam_llr(plan.handle, m, A_SEED, A_IT, A_ROW0, bs, A_NO, _p(f["u"][1]), _p(ubits),
+                                     _p(f["y"][1]), _p(f["llr"][1]), st), "pl_awgn_qam_llr")
+        return f, [ubits]
+    _aligned_equals_shifted(run)
+
+
+@pytest.mark.parametrize("k,e,m", [(12, 20, 2), (100, 180, 2), (20, 90, 6), (100, 184, 8)])
+def test_nr_scalar_store_paths_match_the_vector_paths(pa, k, e, m):
+    """m = 2: pl_nr_awgn_qpsk_llr; m = 6, 8: pl_nr_awgn_qam_llr."""
+    from polar_amd import _lib
+    from test_nr_link_gpu import _pair
+    enc, dec = _pair(k, e)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    g, idx = enc.tables(dev)
+    a, b, fill = dec.tables(dev)
+    plan, n, bs = enc.plan(dev), enc.n_polar, 37
+    null = ctypes.c_void_p(0)
+    tabs = [_p(g), enc.crc_length, _p(idx), e, _p(a), _p(b) if b is not None else null,
+            _p(fill) if fill is not None else null, A_SEED, A_IT, A_ROW0, bs, A_NO]
+    L, st = _lib.lib(), _lib.current_stream_ptr(dev)
+
+    def run(off):
+        f = {"u": _floats(bs * k, off), "llr_ch": _floats(bs * e, off), "llr": _floats(bs * n, off)}
+        ubits = torch.zeros((bs, (k + 31) // 32), dtype=torch.int32, device="cuda")
+        if m == 2:
+            _lib.check(L.pl_nr_awgn_qpsk_llr(plan.handle, k, *tabs, _p(ubits), _p(f["u"][1]), _p(f["llr_ch"][1]),
+                                             _p(f["llr"][1]), st), "pl_nr_awgn_qpsk_llr")
+        else:
+            f["y"] = _floats(bs * (e // m) * 2, off)
+            _lib.check(L.pl_nr_awgn_qam_llr(plan.handle, m, k, *tabs, _p(ubits), _p(f["u"][1]), _p(f["y"][1]),
+                                            _p(f["llr_ch"][1]), _p(f["llr"][1]), st), "pl_nr_awgn_qam_llr")
+        return f, [ubits]
+    _aligned_equals_shifted(run)

@@ -30,7 +30,8 @@ def _kernel_meta(asm, name_pred):
         if not m or not name_pred(m.group(1)):
             continue
         fields = {}
-        for key in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
+        for key in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+                    "group_segment_fixed_size"):
             f = re.search(r"\." + key + r":\s+(\d+)", block)
             fields[key] = int(f.group(1)) if f else None
         out[m.group(1)] = fields
@@ -154,6 +155,46 @@ def test_sc_exact_f_bench_kernel_spill_budget():
     assert m["vgpr_count"] <= 168, m  # 3 waves per SIMD
     assert m["vgpr_spill_count"] <= 6, m
     assert m["private_segment_fixed_size"] <= 32, m
+
+
+# The kernels of channel_kernel.hip, by a substring of the mangled name: (VGPR bound, LDS bytes).  The
+# bound is the VGPR count of the kernels as they were written out one by one (before the producers
+# were assembled from shared phase functions), rounded up to the allocation step of 8: waves per
+# SIMD, 512 // step, cannot drop below what they were.  Counts then: 60, 74, 58, 62, 73, 73, 100, 50,
+# 34, 35, 16.  LDS: the exact layout (4 x kWordsPerWave words; the NR kernels' generator rows, 4 x 192
+# words and 4 x kNrStage stage floats; 16 levels in the QAM kernels; the counting tail's 4 x 2 sums).
+_CHANNEL_KERNELS = {
+    "15awgn_llr_kernelE": (64, 4096),
+    "18nr_awgn_llr_kernelE": (80, 42112),
+    "19awgn_qam_llr_kernelILi4E": (64, 4160),
+    "19awgn_qam_llr_kernelILi8E": (64, 4160),
+    "22nr_awgn_qam_llr_kernelILi4E": (80, 42176),
+    "22nr_awgn_qam_llr_kernelILi6E": (80, 42176),
+    "22nr_awgn_qam_llr_kernelILi8E": (104, 42176),
+    "19count_errors_kernelE": (56, 64),
+    "26count_errors_packed_kernelIfE": (40, 64),
+    "26count_errors_packed_kernelIhE": (40, 64),
+    "16sum_pairs_kernelE": (16, 64),
+}
+
+
+def test_channel_kernels_keep_their_registers_and_lds():
+    """Every kernel of channel_kernel.hip: no spills, no scratch, the LDS bytes of its layout, and
+    at most the VGPRs of its allocation step (_CHANNEL_KERNELS)."""
+    src = os.path.join(_build.CSRC, "channel_kernel.hip")
+    with tempfile.TemporaryDirectory() as td:
+        asm = _compile_asm(src, [], td)
+    meta = _kernel_meta(asm, lambda n: True)
+    assert len(meta) == len(_CHANNEL_KERNELS), sorted(meta)  # a new kernel gets a row above
+    for sub, (vgprs, lds) in _CHANNEL_KERNELS.items():
+        hits = [n for n in meta if sub in n]
+        assert len(hits) == 1, (sub, hits)
+        m = meta[hits[0]]
+        print(hits[0], m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, (sub, m)
+        assert m["private_segment_fixed_size"] == 0, (sub, m)
+        assert m["group_segment_fixed_size"] == lds, (sub, m)
+        assert m["vgpr_count"] <= vgprs, (sub, m)
 
 
 # ---- instruction-stream pins (VERDICT r03 item 7) -------------------------------------------
