@@ -33,6 +33,8 @@
  *   pl_gather_rows   Polar5GEncoder.forward rate matching c[:, ind_rate_matching]
  *                    my_sn/fec/polar/enc.py:378-392
  *   pl_rate_recover  Polar5GDecoder.forward rate recovery my_sn/fec/polar/dec.py:621-654
+ *   pl_osd_plan_create OSDecoder.__init__ my_sn/fec/osd/dec.py:22-53
+ *   pl_osd_decode    OSDecoder.forward  my_sn/fec/osd/dec.py:148-192 (_find_mrb :107-147, _find_min_dist :82-106)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -303,6 +305,42 @@ int pl_nr_awgn_qam_llr(const pl_plan* plan, int32_t bits_per_symbol, int32_t k_t
                        const float* fill, uint64_t seed, uint64_t iteration, int64_t row0, int64_t bs, float no,
                        uint32_t* ubits_out, float* u_out, float* y_out, float* llr_ch_out, float* llr_out,
                        void* hip_stream);
+
+/* Ordered-statistics decoding (OSD) of a short binary linear code: OSDecoder, my_sn/fec/osd/dec.py
+ * (polar_amd.OSDecoder).  Order-t OSD is the usual estimate of the maximum-likelihood curve of a short
+ * code, the yardstick for a list decoder.  One wave decodes one codeword (csrc/osd_kernel.hip):
+ *   1. clip the logits to +-100 and order the positions by |llr| descending -- among equal |llr| the
+ *      lower index first (the reference's argsort leaves that order open);
+ *   2. permute the columns of G into that order and eliminate, for row c = 0 .. k-1 in turn: the pivot
+ *      is the first 1 of row c, row c is XORed into every other row with a 1 there (dec.py:107-147);
+ *   3. hard-decide the k pivot positions (llr > 0 is 1) and re-encode them to c0;
+ *   4. for order i = 1 .. t, every i-subset of the k basis rows in itertools.combinations order: the
+ *      candidate is c0 XOR those rows, its metric mean_j log(1 + exp(llr_j (1 - 2 c_j))); the first
+ *      minimum of an order wins, and replaces the incumbent only when strictly smaller.  The search
+ *      compares the metric differences -sum_{j in supp e} llr_j (1 - 2 c0_j) in fp64, which needs no
+ *      exp or log; a pattern's index counts the orders in turn, each in combinations order.
+ * pl_osd_plan_create: gm is a HOST pointer to the k x n generator matrix, one byte per entry (nonzero
+ *                  = 1), row-major: the encoder applied to the identity (dec.py:38-40).
+ *                  Envelope: 1 <= k <= 128, k <= n <= 256, 0 <= t <= min(k, 4) and at most 2^22 patterns
+ *                  (sum of C(k, i), i = 1 .. t: t = 3 at k = 128 and t = 4 at k = 64 fit, t = 4 at
+ *                  k = 128 does not); PL_ENOTSUP outside it.  PL_EINVAL (the message names the argument)
+ *                  for a NULL pointer, a negative size and a gm that is not of rank k (the reference
+ *                  silently picks column 0 as the pivot of an all-zero row).  These checks run before
+ *                  any HIP call.  The plan is bound to the device current at the call, like a pl_plan;
+ *                  created where there is no GPU, it only answers pl_osd_plan_info.
+ * pl_osd_plan_info: k, n, t and the number of patterns of the search (any pointer may be NULL).
+ * pl_osd_decode:   llr_logits [bs, n] fp32 logits log P(1)/P(0).  out_cw [bs, n]: the decided codeword in
+ *                  channel order, PL_OUT_F32 or PL_OUT_U8.  out_dist (nullable) [bs] fp64: the metric of
+ *                  the returned word.  out_pattern (nullable) [bs] int32: -1 when c0 is returned, else the
+ *                  index of the winning pattern.  No allocation per call; batches above 2^20 rows are
+ *                  launched in chunks.  A stream of another device is PL_EINVAL; bs == 0 is PL_OK.  +-Inf
+ *                  is clipped like any large value; NaN is not supported. */
+typedef struct pl_osd_plan pl_osd_plan;
+int pl_osd_plan_create(pl_osd_plan** out, int32_t k, int32_t n, const uint8_t* gm, int32_t t);
+int pl_osd_plan_destroy(pl_osd_plan* plan);
+int pl_osd_plan_info(const pl_osd_plan* plan, int32_t* k, int32_t* n, int32_t* t, int64_t* n_patterns);
+int pl_osd_decode(const pl_osd_plan* plan, const float* llr_logits, int64_t bs, void* out_cw, int32_t out_kind,
+                  double* out_dist, int32_t* out_pattern, void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

@@ -72,6 +72,10 @@ def _declare(L):
     L.pl_hybrid_workspace_size.restype = ctypes.c_size_t
     L.pl_hybrid_decode.argtypes = [P, P, P, i64, P, i32, P, P, ctypes.POINTER(i64), P, ctypes.c_size_t, P]
     L.pl_crc_status.argtypes = [P, P, i32, i64, P, P]
+    L.pl_osd_plan_create.argtypes = [ctypes.POINTER(P), i32, i32, P, i32]
+    L.pl_osd_plan_destroy.argtypes = [P]
+    L.pl_osd_plan_info.argtypes = [P, P, P, P, P]
+    L.pl_osd_decode.argtypes = [P, P, i64, P, i32, P, P, P]
     L.pl_last_error_string.restype = ctypes.c_char_p
     L.pl_version.restype = ctypes.c_char_p
     for f in (L.pl_plan_create, L.pl_plan_destroy, L.pl_plan_info, L.pl_plan_device, L.pl_sc_decode, L.pl_scl_decode,
@@ -80,7 +84,8 @@ def _declare(L):
               L.pl_gather_rows, L.pl_rate_recover, L.pl_awgn_qpsk_llr, L.pl_count_errors,
               L.pl_awgn_qpsk_llr_bits, L.pl_sc_decode_count, L.pl_sc_sim_count, L.pl_clock_probe,
               L.pl_hybrid_decode, L.pl_crc_status, L.pl_nr_awgn_qpsk_llr, L.pl_count_errors_packed,
-              L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr):
+              L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr, L.pl_osd_plan_create, L.pl_osd_plan_destroy,
+              L.pl_osd_plan_info, L.pl_osd_decode):
         f.restype = ctypes.c_int
     return L
 
@@ -119,6 +124,7 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_sc_count_workspace_size", "pl_sc_decode_count", "pl_sc_sim_count", "pl_clock_probe",
                     "pl_hybrid_workspace_size", "pl_hybrid_decode", "pl_crc_status",
                     "pl_nr_awgn_qpsk_llr", "pl_count_errors_packed", "pl_awgn_qam_llr", "pl_nr_awgn_qam_llr",
+                    "pl_osd_plan_create", "pl_osd_plan_destroy", "pl_osd_plan_info", "pl_osd_decode",
                     "pl_last_error_string", "pl_version")
 
 
@@ -335,6 +341,46 @@ class Plan:
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
             _lib.pl_plan_destroy(h)
+            self._h = None
+
+
+class OsdPlan:
+    """Owning wrapper of a pl_osd_plan* (ordered-statistics decoding of the code with the k x n
+    generator matrix `gm`, order t): immutable, device-bound like Plan.  Where there is no GPU the
+    library makes a host-only plan: k, n, t and n_patterns are there, decoding raises."""
+
+    def __init__(self, gm_u8, t, device=None):
+        import contextlib
+
+        import numpy as np
+        gm = np.ascontiguousarray(gm_u8, dtype=np.uint8)
+        if gm.ndim != 2:
+            raise ValueError(f"gm must be a [k, n] matrix, got shape {gm.shape}")
+        idx = device_index(device)
+        self._h = ctypes.c_void_p()
+        with (torch.cuda.device(idx) if idx is not None else contextlib.nullcontext()):
+            check(lib().pl_osd_plan_create(ctypes.byref(self._h), gm.shape[0], gm.shape[1],
+                                           gm.ctypes.data_as(ctypes.c_void_p), int(t)), "pl_osd_plan_create")
+        k_, n_, t_, np_ = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        check(lib().pl_osd_plan_info(self._h, ctypes.byref(k_), ctypes.byref(n_), ctypes.byref(t_), ctypes.byref(np_)),
+              "pl_osd_plan_info")
+        self.k, self.n, self.t, self.n_patterns = k_.value, n_.value, t_.value, np_.value
+        self.device = torch.device("cuda", idx) if idx is not None else None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __deepcopy__(self, memo):  # a copy would double-free the handle
+        raise TypeError("polar_amd OsdPlan objects are not copyable; build another OsdPlan")
+
+    def __reduce__(self):
+        raise TypeError("polar_amd OsdPlan objects are not picklable")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.pl_osd_plan_destroy(h)
             self._h = None
 
 

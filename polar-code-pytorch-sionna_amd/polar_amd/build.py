@@ -18,7 +18,7 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libpolar_mi355x.so")
 KCACHE = os.path.join(HERE, "kcache")
 SOURCES = ["sc_kernel.hip", "scl_kernel.hip", "encode_kernel.hip", "ratematch_kernel.hip", "channel_kernel.hip",
-           "clock_kernel.hip", "hybrid_kernel.hip", "capi.cpp", "jit.cpp"]
+           "clock_kernel.hip", "hybrid_kernel.hip", "osd_kernel.hip", "capi.cpp", "jit.cpp"]
 # scl_tree_kernel.hip is compiled once per list size (its instantiations, in parallel) and once
 # for the launcher: (object name, source, defines)
 UNITS = [(s + ".o", s, []) for s in SOURCES] + \
@@ -123,7 +123,7 @@ def build(force=False, verbose=False, dev=False):
     hash_h = _write_src_hash(obj_dir)
     deps = [os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "butterfly.h"), os.path.join(CSRC, "softplus.h"),
             os.path.join(CSRC, "exactf.h"),
-            os.path.join(CSRC, "hybrid.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
+            os.path.join(CSRC, "hybrid.h"), os.path.join(CSRC, "osd.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
     jobs = []
     for oname, s, defs in UNITS:
         src = os.path.join(CSRC, s)

@@ -147,6 +147,7 @@ class DenseEncoder(nn.Module):
         fp = frozen_pos.cpu().numpy() if tc.is_tensor(frozen_pos) else np.asarray(frozen_pos)
         self.n = n
         self.info_pos = tc.from_numpy(np.setdiff1d(np.arange(n), fp)).to(device)
+        self.k = int(self.info_pos.numel())  # what OSDecoder asks of an encoder
         self.G = G.to(device)
 
     def forward(self, u):
@@ -163,6 +164,7 @@ class GpuEncoder(nn.Module):
         from . import _lib
         from .frozen import frozen_mask
         self._n, self._mask = n, frozen_mask(frozen_pos, n)
+        self.k = int(n) - int(self._mask.sum())  # what OSDecoder asks of an encoder
         self._plans = _lib.PlanSet()
 
     def _make_plan(self, dev):

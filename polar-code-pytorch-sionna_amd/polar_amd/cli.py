@@ -16,6 +16,9 @@ with --k, --n as k_target, n_target; no counterpart in main.py): the SC leg is d
 scl leg dec_type="SCL" with --list_size (and --hybrid_sc), the LLRs from the fused 5G producer
 (channel.FusedAWGN5G) or, with --llr_producer ops, from the op-by-op chain (System5G_AWGN_model).
 --num_bits_per_symbol 4 / 6 / 8 runs either code over 16-, 64- or 256-QAM (main.py fixes QPSK).
+'osd' in --algos adds the ordered-statistics decoder of order --osd_t (OSDecoder, my_sn/fec/osd/dec.py), the
+estimate of the maximum-likelihood curve: its BLER is comparable with SC / SCL (the encoder is injective), its
+BER counts codeword bits.
 """
 import argparse
 import math
@@ -61,7 +64,18 @@ def parse(argv=None):
                     help="--code 5g, scl leg: SC first, the list decoder only on rows whose CRC fails")
     ap.add_argument("--frozen", choices=["reference", "recompute"], default="reference",
                     help="reference: the pinned sets froze.py produced; recompute: re-run froze.py's recipe")
-    return ap.parse_args(argv)
+    ap.add_argument("--osd_t", type=int, default=2,
+                    help="order of the OSD leg ('osd' in --algos): 0 <= t <= min(k, 4), at most 2^22 patterns")
+    c = ap.parse_args(argv)
+    if "osd" in c.algos:
+        from .osd import check_supported
+        if c.code != "plain":
+            ap.error("'osd' in --algos needs --code plain")
+        try:
+            check_supported(c.k, c.n, c.osd_t)
+        except ValueError as e:
+            ap.error(str(e))
+    return c
 
 
 def set_seed(seed):  # main.py:24-29
@@ -113,16 +127,20 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
         dec = SC_Dec(fp, c.n, device=dev_str)
     elif mode == "scl":
         dec = SCL_Dec(fp, c.n, c.list_size, device=dev_str)
+    elif mode == "osd":  # decides codewords: the model compares them with the transmitted ones
+        from .osd import OSDecoder
+        dec = OSDecoder(c.osd_t, enc, device=dev_str)
     else:
         raise Exception('error...')
+    cw = mode == "osd"
     if device.type == "cuda" and getattr(c, "llr_producer", "fused") == "fused":
         # one HIP launch for bits/encoder/mapper/channel/demapper; rank r draws stream rows
         # [r*bs, (r+1)*bs) of the seed's stream
         rank = int(os.environ.get("RANK", "0"))
-        model = channel.FusedAWGN(c.n, c.k, fp, dec, device=device, seed=c.seed, row0=rank * c.bs,
+        model = channel.FusedAWGN(c.n, c.k, fp, dec, device=device, seed=c.seed, row0=rank * c.bs, cw_estimates=cw,
                                   num_bits_per_symbol=getattr(c, "num_bits_per_symbol", 2))
     else:
-        model = channel.System_AWGN_model(c.n, c.k, enc, dec, device=device, generator=generator,
+        model = channel.System_AWGN_model(c.n, c.k, enc, dec, cw_estimates=cw, device=device, generator=generator,
                                           num_bits_per_symbol=getattr(c, "num_bits_per_symbol", 2))
     return [model, name]
 
@@ -151,6 +169,8 @@ def main(argv=None):
     codes = [gen_code(c, "SC", "sc", device, gen)]
     if "scl" in c.algos:
         codes.append(gen_code(c, f"SCL-{c.list_size}", "scl", device, gen))
+    if "osd" in c.algos:
+        codes.append(gen_code(c, f"OSD-{c.osd_t} (codeword BER)", "osd", device, gen))
     plot = PlotBER(f"Performance of Short Len Codes (k={c.k}, n={c.n})")
     results = {}
     for model, name in codes:

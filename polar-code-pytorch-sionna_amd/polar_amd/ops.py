@@ -162,6 +162,36 @@ def crc_status(plan, bits):
     return valid != 0
 
 
+def osd_decode(plan, llr_logits, out=None, out_dtype=torch.float32, return_dist=False, return_pattern=False):
+    """Ordered-statistics decode (pl_osd_decode, plan: _lib.OsdPlan) of [bs, n] fp32 logits
+    log P(1)/P(0) -> [bs, n] codeword bits in channel order (my_sn/fec/osd/dec.py:148-192).
+    return_dist: also the fp64 metric [bs] of each returned word (the mean softplus of dec.py:68-81);
+    return_pattern: also int32 [bs], -1 where the re-encoded hard decision c0 won, else the index of
+    the winning error pattern (orders 1 .. t in turn, each in itertools.combinations order)."""
+    _require_cuda(llr_logits, "llr_logits")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != plan.n:
+        raise ValueError(f"llr_logits must be [bs, {plan.n}], got {tuple(x.shape)}")
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.n), dtype=out_dtype, device=x.device)
+    elif out.shape != (bs, plan.n) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, n] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+    dist = torch.empty((bs,), dtype=torch.float64, device=x.device) if return_dist else None
+    pat = torch.empty((bs,), dtype=torch.int32, device=x.device) if return_pattern else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_osd_decode(plan.handle, ctypes.c_void_p(x.data_ptr()), bs,
+                                            ctypes.c_void_p(out.data_ptr()), kind,
+                                            ctypes.c_void_p(dist.data_ptr() if return_dist else 0),
+                                            ctypes.c_void_p(pat.data_ptr() if return_pattern else 0),
+                                            _lib.current_stream_ptr(x.device)), "pl_osd_decode")
+    res = (out,) + ((dist,) if return_dist else ()) + ((pat,) if return_pattern else ())
+    return res if len(res) > 1 else out
+
+
 def polar_encode(plan, u_bits, out=None):
     """Encode [bs, k] 0/1 fp32 information bits -> [bs, n] fp32 codewords (enc.py:30-43)."""
     _require_cuda(u_bits, "u_bits")
