@@ -116,3 +116,117 @@ def test_noiseless_round_trip(g, dec_type):
         flip = torch.from_numpy(rng.random((40, n)) < 0.5).cuda()
         _, ok2 = dec(torch.where(flip, -logits, logits))
         assert float(ok2.mean()) < 0.5, (k, n)
+
+
+# ---- the op-by-op kernels past one row per block -------------------------------------------------
+# pl_gather_rows and pl_rate_recover take bs // 2048 (1 ... 8) rows per block; the fixtures and the
+# link tests stay below 2048 rows, where the row loop runs once and its `b >= bs` exit is never taken.
+
+def _np_parity(u, name):
+    """[information bits | parity] in numpy: parity = XOR of crc_generator_rows of the 1 bits."""
+    from polar_amd import polar5g
+    deg = polar5g.mysn.crc_params(name)[0]
+    rows = polar5g.crc_generator_rows(name, u.shape[1])
+    acc = np.bitwise_xor.reduce(np.where(u.astype(bool), rows[None, :], 0).astype(np.uint32), axis=1)
+    return np.concatenate([u, ((acc[:, None] >> np.arange(deg)[None, :]) & 1).astype(np.float32)], 1)
+
+
+@pytest.mark.parametrize("bs", [4099, 16389])  # 2 and 8 rows per block, the last block ragged
+@pytest.mark.parametrize("k,e", [(12, 20), (64, 200), (300, 1088)])  # shortening, puncturing, repetition
+def test_row_loop_of_gather_and_rate_recover(k, e, bs):
+    import oracle
+    from polar_amd import polar5g
+    assert torch.cuda.is_available()
+    enc = _quiet(polar5g.Polar5GEncoder, k, e)
+    dec = _quiet(polar5g.Polar5GDecoder, enc, dec_type="SC")
+    rng = np.random.default_rng([k, e, bs])
+    u = rng.integers(0, 2, (bs, k)).astype(np.float32)
+    want = oracle.polar_encode(_np_parity(u, enc.crc_degree), enc.frozen_pos, enc.n_polar)[:, enc._ind_rate_matching]
+    assert np.array_equal(enc(torch.from_numpy(u).cuda()).cpu().numpy(), want)
+    a, b, f = dec._rec
+    kinds = {(12, 20): (f != 0).any(), (64, 200): ((a < 0) & (f == 0)).any(), (300, 1088): (b >= 0).any()}
+    assert kinds[k, e]
+    x = rng.standard_normal((bs, e)).astype(np.float32)
+    rec = np.where(a[None, :] >= 0, x[:, np.maximum(a, 0)], f[None, :])
+    rep = b >= 0
+    rec[:, rep] = x[:, a[rep]] + x[:, b[rep]]
+    assert np.array_equal(dec.rate_recover(torch.from_numpy(x).cuda()).cpu().numpy(), rec.astype(np.float32))
+
+
+@pytest.mark.parametrize("bs", [1, 3, 4, 5, 4099])  # a block takes 4 rows, one per wave
+@pytest.mark.parametrize("k,name", [(12, "CRC6"), (300, "CRC11")])
+def test_crc_attach_and_status_at_the_block_edge(k, name, bs):
+    from polar_amd import _lib, ops, polar5g
+    assert torch.cuda.is_available()
+    enc = _quiet(polar5g.Polar5GEncoder, k, 1088 if k == 300 else 20)
+    assert enc.crc_degree == name
+    deg, poly = polar5g.mysn.crc_params(name)
+    rng = np.random.default_rng([k, bs])
+    u = rng.integers(0, 2, (bs, k)).astype(np.float32)
+    want = _np_parity(u, name)
+    got = enc.crc_attach(torch.from_numpy(u).cuda())
+    assert np.array_equal(got.cpu().numpy(), want)
+    # pl_crc_status on a plan that carries (k + degree, CRC): the attached words pass; with one bit
+    # flipped in every other row, a row passes iff its parity is still that of its information bits
+    n = 1 << (k + deg - 1).bit_length()
+    mask = np.zeros(n, dtype=np.uint8)
+    mask[: n - (k + deg)] = 1
+    plan = _lib.Plan(n, mask, 1, _lib.PL_F_MINSUM, flags=_lib.PL_PLAN_GENERIC)
+    plan.set_crc(deg, poly)
+    assert bool(ops.crc_status(plan, got).all())
+    bad = want.copy()
+    flip = np.arange(bs) % 2 == 0
+    col = rng.integers(0, k + deg, bs)
+    bad[flip, col[flip]] = 1 - bad[flip, col[flip]]
+    ok = (_np_parity(bad[:, :k], name) == bad).all(axis=1)
+    assert np.array_equal(ok, ~flip)  # a single flip never passes
+    assert np.array_equal(ops.crc_status(plan, torch.from_numpy(bad).cuda()).cpu().numpy(), ok)
+
+
+def test_gather_and_rate_recover_column_limits():
+    """Through the C entry points: the largest table the kernels stage in LDS is accepted and gives the
+    right rows (4099 rows: two per block), one more column is PL_EINVAL."""
+    import ctypes
+
+    from polar_amd import _lib
+    assert torch.cuda.is_available()
+    L, st = _lib.lib(), _lib.current_stream_ptr(torch.device("cuda", torch.cuda.current_device()))
+    rng = np.random.default_rng(4096)
+    bs = 4099
+
+    def p(t):
+        return ctypes.c_void_p(t.data_ptr())
+
+    n_in = 1000
+    x = rng.standard_normal((bs, n_in)).astype(np.float32)
+    xd = torch.from_numpy(x).cuda()
+    for n_out, rc in ((4096, _lib.PL_OK), (4097, _lib.PL_EINVAL)):
+        idx = rng.integers(0, n_in, n_out).astype(np.int32)
+        out = torch.full((bs, n_out), float("nan"), device="cuda")
+        idx_d = torch.from_numpy(idx).cuda()  # named: a table must outlive the launch that reads it
+        assert L.pl_gather_rows(p(xd), bs, n_in, p(idx_d), n_out, p(out), st) == rc, n_out
+        torch.cuda.synchronize()
+        if rc == _lib.PL_OK:
+            assert np.array_equal(out.cpu().numpy(), x[:, idx])
+        else:
+            assert b"pl_gather_rows" in L.pl_last_error_string() and bool(torch.isnan(out).all())
+    e = 1500
+    y = rng.standard_normal((bs, e)).astype(np.float32)
+    yd = torch.from_numpy(y).cuda()
+    for n, rc in ((2048, _lib.PL_OK), (2049, _lib.PL_EINVAL)):
+        a = rng.integers(-1, e, n).astype(np.int32)
+        b = np.where(rng.random(n) < 0.3, rng.integers(0, e, n), -1).astype(np.int32)
+        f = rng.standard_normal(n).astype(np.float32)
+        out = torch.full((bs, n), float("nan"), device="cuda")
+        a_d, b_d, f_d = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), torch.from_numpy(f).cuda()
+        assert a_d.data_ptr() != b_d.data_ptr() != f_d.data_ptr()
+        got = L.pl_rate_recover(p(yd), bs, e, p(a_d), p(b_d), p(f_d), n, p(out), st)
+        assert got == rc, n
+        torch.cuda.synchronize()
+        if rc == _lib.PL_OK:
+            want = np.where(a[None, :] >= 0, y[:, np.maximum(a, 0)], f[None, :])
+            both = (a >= 0) & (b >= 0)
+            want[:, both] = y[:, a[both]] + y[:, b[both]]
+            assert np.array_equal(out.cpu().numpy(), want.astype(np.float32))
+        else:
+            assert b"pl_rate_recover" in L.pl_last_error_string() and bool(torch.isnan(out).all())
