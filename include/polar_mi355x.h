@@ -342,6 +342,26 @@ int pl_osd_plan_info(const pl_osd_plan* plan, int32_t* k, int32_t* n, int32_t* t
 int pl_osd_decode(const pl_osd_plan* plan, const float* llr_logits, int64_t bs, void* out_cw, int32_t out_kind,
                   double* out_dist, int32_t* out_pattern, void* hip_stream);
 
+/* Genie-aided SC for frozen-set design (polar_amd.design; csrc/genie_kernel.hip): the leaf LLR of every
+ * position when all earlier bits are fed back correctly.
+ * llr_logits [bs, n] fp32 logits log P(1)/P(0) (negated inside, as pl_sc_decode).
+ * u_bits [bs, ceil(n/32)] uint32: the u-domain word, ALL n positions (bit m%32 of word m/32 =
+ * position m; frozen positions carry their value, normally 0).
+ * counts (nullable) [n] int64 device counters, accumulated: counts[i] += rows where
+ * HD(leaf[i]) != u[i], HD(x) = !(x > 0).
+ * leaf_out (nullable) [bs, n] fp32: the leaf LLRs alpha_0 (positive favours 0).
+ * The transform, in place on a[0..n) = -logits, S = log2 n: beta_0 = u; beta_s is beta_{s-1} with
+ * b[p] ^= b[p + 2^(s-1)] for every p whose index bit s-1 is 0 (the encoder butterfly stopped after s
+ * stages); for s = S down to 1, h = 2^(s-1), every p whose index bit s-1 is 0: x = a[p], y = a[p+h],
+ * a[p] = f(x, y), a[p+h] = g(x, y, beta_{s-1}[p]), f and g those of pl_sc_decode (min-sum on inputs
+ * clipped to +-llr_max, or the exact f of PL_F_EXACT, full-range form when llr_max > 43; g unclipped,
+ * one rounding).  After stage 1, a is the leaf vector.  counts[] is a sum of integers: reproducible.
+ * n a power of two, 2 <= n <= 2048; bs == 0 is PL_OK; PL_EINVAL (the message names the argument) for a
+ * bad n or f_mode, a NULL llr_logits or u_bits with bs > 0, both outputs NULL, negative bs.  No plan:
+ * the stream's device is the caller's business, as for pl_crc_attach.  No allocation per call. */
+int pl_genie_count(int32_t n, int32_t f_mode, float llr_max, const float* llr_logits, const uint32_t* u_bits,
+                   int64_t bs, int64_t* counts, float* leaf_out, void* hip_stream);
+
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)
  * and ticks[2] (the chain's result) to the DEVICE buffer ticks[3]; clock GHz = 0.1 * ticks[0] /

@@ -62,8 +62,11 @@ def parse(argv=None):
                          "k_target, n_target (CRC, rate matching)")
     ap.add_argument("--hybrid_sc", action="store_true",
                     help="--code 5g, scl leg: SC first, the list decoder only on rows whose CRC fails")
-    ap.add_argument("--frozen", choices=["reference", "recompute"], default="reference",
-                    help="reference: the pinned sets froze.py produced; recompute: re-run froze.py's recipe")
+    ap.add_argument("--frozen", choices=["reference", "recompute", "design"], default="reference",
+                    help="reference: the pinned sets froze.py produced; recompute: re-run froze.py's recipe; design: "
+                         "genie-aided Monte-Carlo SC construction at --design_ebno (polar_amd.design; --code plain, GPU)")
+    ap.add_argument("--design_ebno", type=float, default=None, help="--frozen design: the Eb/N0 (dB) to design for")
+    ap.add_argument("--design_rows", type=int, default=2 ** 20, help="--frozen design: codewords of the design run")
     ap.add_argument("--osd_t", type=int, default=2,
                     help="order of the OSD leg ('osd' in --algos): 0 <= t <= min(k, 4), at most 2^22 patterns")
     c = ap.parse_args(argv)
@@ -75,7 +78,31 @@ def parse(argv=None):
             check_supported(c.k, c.n, c.osd_t)
         except ValueError as e:
             ap.error(str(e))
+    if c.frozen == "design":
+        if c.design_ebno is None:
+            ap.error("--frozen design needs --design_ebno")
+        if c.code != "plain":
+            ap.error("--frozen design needs --code plain")
+        if c.llr_device != "cuda":
+            ap.error("--frozen design runs on the GPU (--llr_device cuda)")
+        if c.design_rows < 1:
+            ap.error("--design_rows must be >= 1")
     return c
+
+
+def designed_frozen_pos(c, device):
+    """--frozen design: the set designed once per run (kept on the parsed arguments), so every leg
+    decodes the same code; returns (frozen_pos, hash, union bound estimate)."""
+    if getattr(c, "_designed", None) is None:
+        import hashlib
+        from . import design
+        counts, rows = design.bit_channel_errors(c.n, c.k, c.design_ebno, c.design_rows,
+                                                 num_bits_per_symbol=getattr(c, "num_bits_per_symbol", 2),
+                                                 seed=c.seed, device=device)
+        fp = design.select_frozen(counts, c.k)
+        digest = hashlib.sha256(fp.numpy().astype("<i8").tobytes()).hexdigest()[:16]
+        c._designed = (fp, digest, design.union_bound(counts, rows, fp))
+    return c._designed
 
 
 def set_seed(seed):  # main.py:24-29
@@ -118,6 +145,11 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
             fp = frozen.reference_frozen_pos(c.k, c.n)
         except KeyError:
             pass
+    elif c.frozen == "design":
+        fp, digest, ub = designed_frozen_pos(c, device)
+        if int(os.environ.get("RANK", "0")) == 0:
+            print(f"{name}: frozen set designed at {c.design_ebno} dB over {c.design_rows} rows, hash {digest}, "
+                  f"union bound {ub:.3e}")
     if device.type == "cuda":
         enc = channel.GpuEncoder(fp, c.n)
     else:

@@ -416,6 +416,45 @@ def count_errors_packed(bits, ref_bits, k_cmp=None, counts=None):
     return counts
 
 
+def genie_count(n, llr_logits, u_bits, f_mode=0, llr_max=30.0, counts=None, return_leaf=False):
+    """pl_genie_count: genie-aided SC of [bs, n] fp32 logits whose u-domain words are u_bits ([bs,
+    ceil(n/32)] int32, ALL n positions packed as pack_bits does): counts[i] += the rows whose leaf
+    LLR at position i decides against u[i] when every earlier bit is fed back correctly.  counts:
+    int64 [n] on the input's device, accumulated into (created if None; False: no counting, with
+    return_leaf).  Returns counts, or (counts, leaf [bs, n] fp32: positive favours 0) with return_leaf."""
+    _require_cuda(llr_logits, "llr_logits")
+    n = int(n)
+    if n < 2 or n > 2048 or n & (n - 1):
+        raise ValueError(f"n must be a power of two in [2, 2048], got {n}")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != n:
+        raise ValueError(f"llr_logits must be [bs, {n}], got {tuple(x.shape)}")
+    bs, nq = x.shape[0], (n + 31) // 32
+    if not isinstance(u_bits, torch.Tensor) or u_bits.shape != (bs, nq) or u_bits.dtype != torch.int32 \
+            or u_bits.device != x.device:
+        raise ValueError(f"u_bits must be int32 [{bs}, {nq}] on the input's device")
+    u = u_bits.contiguous()
+    if counts is False:
+        if not return_leaf:
+            raise ValueError("counts=False needs return_leaf=True: nothing to compute")
+        counts = None
+    elif counts is None:
+        counts = torch.zeros(n, dtype=torch.int64, device=x.device)
+    elif not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or not counts.is_contiguous() \
+            or counts.shape != (n,) or counts.device != x.device:
+        raise ValueError(f"counts must be a contiguous int64 [{n}] tensor on {x.device}")
+    leaf = torch.empty((bs, n), dtype=torch.float32, device=x.device) if return_leaf else None
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_genie_count(n, int(f_mode), float(llr_max), ptr(x), ptr(u), bs, ptr(counts), ptr(leaf),
+                                             _lib.current_stream_ptr(x.device)), "pl_genie_count")
+    return (counts, leaf) if return_leaf else counts
+
+
 def pack_bits(bits):
     """[..., k] 0/1 tensor -> [rows, ceil(k/32)] int32 words in pl_sc_decode_count's layout."""
     k = bits.shape[-1]
