@@ -9,7 +9,8 @@
 //   basis     row r of G with its columns in that order lives in lane r % 64, slot r / 64, as NW
 //             words (bits past n zero).  NW and the slots per lane are template parameters, so every
 //             row word has a compile-time register index.  All NW in {1, 2, 4, 8} x slots in {1, 2} are
-//             instantiated; <1, 2> is never launched (two slots mean k > 64, hence n > 32).
+//             instantiated; <1, 2> and <2, 2> are never launched (two slots mean k > 64, hence n >= 65
+//             and NW >= 4).
 //   eliminate for row c = 0 .. k-1 in turn (dec.py:115-127): the row is broadcast with lane reads, its
 //             first set bit p is the pivot (wave-uniform), every other row with bit p set XORs it in.
 //   c0        hard decision of the k pivot positions (llr > 0), c0 = XOR of the rows whose bit is 1.

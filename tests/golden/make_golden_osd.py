@@ -32,11 +32,7 @@ sys.path.insert(0, OUT)
 import osd_ref  # noqa: E402
 
 
-def random_full_rank(k, n, rng):
-    while True:
-        g = rng.integers(0, 2, (k, n)).astype(np.uint8)
-        if osd_ref.gf2_rank(g) == k:
-            return g
+random_full_rank = osd_ref.random_full_rank
 
 
 class DenseEncoder:

@@ -17,8 +17,15 @@ Since softplus(x) - softplus(-x) = x, the metric of c0 ^ e minus that of c0 is D
 Delta(e) = -sum_{j in supp e} llr_j (1 - 2 c0_j): the search below compares Delta in fp64 (the lexicographic
 minimum of (Delta, pattern index) with Delta < 0 required) and evaluates the softplus form once, for the
 returned word.  A pattern's index counts the orders in turn, each in combinations order; -1 means c0.
+
+osd_decode is the statement of the contract: a dense [rows, patterns, n] search.  osd_decode_packed is its
+accelerator for the shapes the dense one cannot hold (tests/test_osd.py proves the two equal), and
+envelope_case builds the inputs of tests/test_osd_envelope_gpu.py, whose conditions tests/test_osd.py
+asserts without a GPU.
 """
+import functools
 import itertools
+import math
 
 import numpy as np
 
@@ -50,6 +57,39 @@ def polar_like(k, n):
         g = np.kron(g, f)
     order = np.argsort(-g.sum(1), kind="stable")
     return (g[np.sort(order[:k])] % 2).astype(np.uint8)
+
+
+def random_full_rank(k, n, rng):
+    """A uniformly drawn 0/1 matrix [k, n] of rank k (redrawn until it is)."""
+    while True:
+        g = rng.integers(0, 2, (k, n)).astype(np.uint8)
+        if gf2_rank(g) == k:
+            return g
+
+
+def tie_rows(n, rng):
+    """Rows that exercise the tie policy; all values are multiples of 2^-6 below 2^7, so every Delta
+    is an exact fp64 sum whatever its order."""
+    rows = []
+    for v in (0.5, 3.0, 100.0):  # all-equal |llr|
+        rows += [np.full(n, v) * rng.choice([-1.0, 1.0], n) for _ in range(8)]
+    for _ in range(16):  # clipped to +-100 in half the positions
+        r = np.round(rng.normal(0, 4, n) * 64) / 64
+        half = rng.permutation(n)[: n // 2]
+        r[half] = rng.choice([-1.0, 1.0], n // 2) * rng.choice([100.0, 250.0, 1e6], n // 2)
+        rows.append(r)
+    for _ in range(16):  # exact zeros of either sign: hard decision 0, tie among themselves
+        r = np.round(rng.normal(0, 4, n) * 64) / 64
+        z = rng.permutation(n)[: n // 3]
+        r[z] = rng.choice([0.0, -0.0], z.size)
+        rows.append(r)
+    for _ in range(16):  # +-Inf is clipped like any large value
+        r = np.round(rng.normal(0, 4, n) * 64) / 64
+        z = rng.permutation(n)[: n // 4]
+        r[z] = rng.choice([-np.inf, np.inf], z.size)
+        rows.append(r)
+    rows.append(np.zeros(n))
+    return np.array(rows, dtype=np.float32)
 
 
 def awgn_logits(g, rows, ebno_db, rng):
@@ -160,3 +200,186 @@ def osd_decode(gm, llr, t, chunk_elems=1 << 23):
         np.put_along_axis(o, idx, cw, axis=1)
         out[sl] = o
     return out, dist, pattern, gap
+
+
+@functools.lru_cache(maxsize=8)
+def packed_patterns(k, i):
+    """The i-subsets of range(k) in itertools.combinations order as a read-only array [C(k, i), i],
+    filled straight from the iterator (no list of tuples); uint8 where the members fit."""
+    count = math.comb(k, i)
+    flat = np.fromiter(itertools.chain.from_iterable(itertools.combinations(range(k), i)),
+                       dtype=np.uint8 if k <= 256 else np.int64, count=count * i)
+    p = flat.reshape(count, i)
+    p.setflags(write=False)
+    return p
+
+
+_BYTE_BITS = ((np.arange(256)[:, None] >> np.arange(8)) & 1).astype(np.float64)  # [value, bit]
+
+
+def osd_decode_packed(gm, llr, t, block=1 << 16):
+    """osd_decode with a bit-packed search: the same four results, for shapes whose dense
+    [rows, patterns, n] candidates do not fit (about 1e-7 s a pattern at n <= 256).
+    The basis, c0 and a are the dense function's.  The basis rows are packed eight positions a byte
+    (little end first), a candidate is the XOR of packed rows, and its Delta is the fp64 sum, in byte
+    order, of one look-up per byte in a table whose entry v of byte b is -sum a[8 b + i] over the bits i
+    of v.  First argmin within an order, strict < between orders; the gap is between the two smallest of
+    {0} and all Deltas."""
+    gm = (np.asarray(gm) != 0).astype(np.uint8)
+    k, n = gm.shape
+    llr = np.asarray(llr, dtype=np.float32).reshape(-1, n)
+    bs = llr.shape[0]
+    nb = (n + 7) // 8
+    out = np.zeros((bs, n), dtype=np.uint8)
+    dist = np.zeros(bs, dtype=np.float64)
+    pattern = np.full(bs, -1, dtype=np.int32)
+    gap = np.full(bs, np.inf, dtype=np.float64)
+    for lo in range(0, bs, 64):
+        sl = slice(lo, min(bs, lo + 64))
+        g, idx, ls = most_reliable_basis(gm, llr[sl])
+        m = g.shape[0]
+        u = (ls[:, :k] > 0).astype(np.uint8)
+        c0 = (u[:, :, None] & g).sum(axis=1, dtype=np.int64).astype(np.uint8) & 1  # [m, n]
+        a = ls.astype(np.float64) * (1.0 - 2.0 * c0)
+        packed = np.packbits(g, axis=2, bitorder="little")  # [m, k, nb]
+        a8 = np.zeros((m, nb * 8), dtype=np.float64)
+        a8[:, :n] = a
+        tab = -np.einsum("mbi,vi->mbv", a8.reshape(m, nb, 8), _BYTE_BITS)  # [m, nb, 256]
+        cw = c0.copy()
+        for r in range(m):
+            best, best_g, members = 0.0, -1, ()
+            low = [np.zeros(1)]
+            base = 0
+            for i in range(1, min(t, k) + 1):
+                p = packed_patterns(k, i)
+                dmin, amin = np.inf, -1
+                for s in range(0, len(p), block):
+                    q = p[s:s + block]
+                    e = packed[r, q[:, 0]]
+                    for j in range(1, i):
+                        e = e ^ packed[r, q[:, j]]
+                    d = tab[r, 0][e[:, 0]]
+                    for b in range(1, nb):
+                        d += tab[r, b][e[:, b]]
+                    am = int(np.argmin(d))  # the first minimum of the block
+                    if d[am] < dmin:  # and, by strict <, of the order
+                        dmin, amin = float(d[am]), s + am
+                    low.append(np.partition(d, 1)[:2] if d.size > 1 else d)
+                if dmin < best:
+                    best, best_g, members = dmin, base + amin, tuple(int(x) for x in p[amin])
+                base += len(p)
+            for j in members:
+                cw[r] ^= g[r, j]
+            pattern[lo + r] = best_g
+            if base:
+                two = np.partition(np.concatenate(low), 1)[:2]
+                gap[lo + r] = two[1] - two[0]
+        z = ls.astype(np.float64) * (1.0 - 2.0 * cw)
+        dist[sl] = np.logaddexp(0.0, z).mean(axis=1)
+        o = np.zeros((m, n), dtype=np.uint8)
+        np.put_along_axis(o, idx, cw, axis=1)
+        out[sl] = o
+    return out, dist, pattern, gap
+
+
+def structured_g():
+    """(16, 40): [I16 | 8 all-zero columns | 16 columns that repeat earlier ones], what shortening and
+    repetition produce.  Among the sorted columns the first 16 are dependent, so the pivots skip."""
+    rng = np.random.default_rng(1640)
+    eye = np.eye(16, dtype=np.uint8)
+    return np.concatenate([eye, np.zeros((16, 8), dtype=np.uint8), eye[:, rng.integers(0, 16, 16)]], axis=1)
+
+
+def planted_rows(g, orders, rng, first_rows=False):
+    """One row per order i: a codeword of g with distinct magnitudes in [4, 8] and i signs flipped, so
+    that c0 carries i wrong bits where the flipped positions are pivots.  The flipped positions are the i
+    most reliable ones, or with first_rows the pivots of the basis rows 0 .. i-1, which makes the
+    codeword the first pattern of order i.  What wins is for the reference to say."""
+    k, n = g.shape
+    rows = []
+    for i in orders:
+        c = (rng.integers(0, 2, k) @ g.astype(np.int64)) % 2
+        mag = rng.uniform(4.0, 8.0, n).astype(np.float32)
+        assert len(np.unique(mag)) == n
+        r = mag * (2.0 * c - 1.0).astype(np.float32)
+        if first_rows:
+            flip = most_reliable_basis(g, r[None])[1][0, :i]  # the basis depends on |llr| alone
+        else:
+            flip = np.argsort(-mag)[:i]
+        r[flip] *= -1.0
+        rows.append(r)
+    return np.array(rows, dtype=np.float32).reshape(-1, n)
+
+
+def weak_pivot_row(g, i, rng):
+    """A row meant to be won by a pattern of order i where the code's rate leaves planted_rows no chance
+    (few redundant positions): a codeword whose positions up to the last i pivots of a random order are
+    strong (distinct magnitudes in [32, 64]) and from there on weak ([4, 4.4]), with the signs of those i
+    pivots flipped.  Only the basis rows of the weak pivots are then worth flipping, and all i of them
+    are when every sum of a subset of them outweighs the subset on the weak redundant positions."""
+    k, n = g.shape
+    order = rng.permutation(n)
+    mag = np.empty(n, dtype=np.float32)
+    mag[order] = np.linspace(64.0, 32.0, n, dtype=np.float32)
+    flip = most_reliable_basis(g, mag[None])[1][0, :k]  # the pivots, as channel indices
+    rank = np.empty(n, dtype=np.int64)
+    rank[order] = np.arange(n)
+    flip = flip[np.argsort(rank[flip])[k - i:]]  # the i pivots that come last in the order
+    weak = order[rank[flip].min():]
+    mag[weak] = np.linspace(4.4, 4.0, len(weak), dtype=np.float32)
+    c = (rng.integers(0, 2, k) @ g.astype(np.int64)) % 2
+    r = mag * (2.0 * c - 1.0).astype(np.float32)
+    r[flip] *= -1.0
+    return r[None]
+
+
+# name: (k, n, t, generator matrix, Eb/N0 dB of the AWGN rows, their number, seed, tie rows?, weak-pivot rows
+# as (order, seed)).  Every case with tie rows and t >= 2 also gets planted_rows of the orders 1 .. t and,
+# with first_rows, of the orders 2 .. t.  Eb/N0 and the seeds were chosen on the CPU for the conditions that
+# tests/test_osd.py::test_envelope_inputs_meet_their_conditions asserts.
+ENVELOPE_CASES = {
+    "k10n20t2": (10, 20, 2, "random", 0.0, 48, 3, True, ()),
+    "k8n16t3": (8, 16, 3, "random", 0.0, 48, 1, True, ((3, 1),)),
+    "k12n24t4": (12, 24, 4, "random", 0.0, 48, 5, True, ((4, 2),)),
+    "k24n33t4": (24, 33, 4, "random", -2.0, 48, 1, True, ((4, 4),)),
+    "k40n200t3": (40, 200, 3, "random", 0.0, 48, 1, True, ()),
+    "k66n97t3": (66, 97, 3, "random", 0.0, 48, 1, True, ()),
+    "k70n130t2": (70, 130, 2, "random", 0.0, 48, 1, True, ()),
+    "k128n128t2": (128, 128, 2, "random", 0.0, 48, 1, True, ()),
+    "k16n40t2_structured": (16, 40, 2, "structured", 0.0, 48, 1, True, ()),
+    "k16n40t2_structured_permuted": (16, 40, 2, "structured_permuted", 0.0, 48, 1, True, ()),
+    "k64n128t4": (64, 128, 4, "random", 0.0, 4, 2, False, ()),
+    "k128n256t3": (128, 256, 3, "random", 1.0, 4, 1, False, ()),
+    "k100n104t4": (100, 104, 4, "random", -2.0, 3, 9, False, ((3, 12),)),
+}
+ENVELOPE_CORNERS = ("k64n128t4", "k128n256t3", "k100n104t4")
+
+
+def envelope_case(name):
+    """The inputs of an envelope case, rebuilt from its seed: (g uint8 [k, n], t, llr fp32 [rows, n],
+    exact bool [rows]).  exact marks the tie rows, whose Deltas are exact in any order; every other row
+    must lead its runner-up by more than 1e-9."""
+    k, n, t, kind, ebno, rows, seed, ties, weak = ENVELOPE_CASES[name]
+    rng = np.random.default_rng([seed, k, n, t])
+    if kind == "random":
+        g = random_full_rank(k, n, rng)
+    else:
+        g = structured_g()
+        if kind == "structured_permuted":
+            g = g[:, np.random.default_rng(4016).permutation(n)]
+    llr = [awgn_logits(g, rows, ebno, rng)[0]]
+    if t >= 2 and ties:
+        llr.append(planted_rows(g, range(1, t + 1), rng))
+        llr.append(planted_rows(g, range(2, t + 1), rng, first_rows=True))
+    llr += [weak_pivot_row(g, i, np.random.default_rng([s, k, n, i])) for i, s in weak]
+    inexact = sum(len(x) for x in llr)
+    if ties:
+        llr.append(tie_rows(n, rng))
+    llr = np.concatenate(llr, axis=0)
+    return g, t, llr, np.arange(len(llr)) >= inexact
+
+
+def winner_orders(pattern, k, t):
+    """The order of each winning pattern index (0 for c0, pattern -1)."""
+    starts = np.cumsum([0] + [math.comb(k, i) for i in range(1, t + 1)])
+    return np.searchsorted(starts, np.asarray(pattern), side="right")

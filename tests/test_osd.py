@@ -2,6 +2,7 @@
 results, OSDecoder's constructor checks, the argument checks of pl_osd_plan_create (they run before
 any HIP call) and the command-line options."""
 import ctypes
+import itertools
 import math
 import os
 import sys
@@ -210,3 +211,125 @@ def test_cli_builds_the_osd_leg_on_the_cpu_llr_path():
     if not torch.cuda.is_available():
         with pytest.raises(RuntimeError):  # decoding itself needs the GPU
             model(5, 2.0)
+
+
+def _assert_packed_equals_dense(g, llr, t, exact):
+    cw, dist, pattern, gap = osd_ref.osd_decode(g, llr, t)
+    cw2, dist2, pattern2, gap2 = osd_ref.osd_decode_packed(g, llr, t)
+    assert np.array_equal(cw2, cw) and np.array_equal(pattern2, pattern)
+    assert cw2.dtype == cw.dtype and pattern2.dtype == pattern.dtype and dist2.dtype == np.float64
+    assert np.allclose(dist2, dist, rtol=1e-12, atol=0)
+    assert np.array_equal(gap2[exact], gap[exact])  # every Delta of these rows is exact: the same gap
+    both = np.isfinite(gap)
+    assert np.array_equal(both, np.isfinite(gap2))
+    assert np.all(np.abs(gap2[both] - gap[both]) <= 1e-12)
+
+
+@pytest.mark.parametrize("name", _names())
+def test_packed_search_equals_the_dense_one_on_the_fixtures(name):
+    with np.load(GOLDEN) as d:
+        g, llr = d[name + "_G"], d[name + "_llr"]
+    _assert_packed_equals_dense(g, llr, int(name.split("t")[-1]), np.zeros(len(llr), dtype=bool))
+
+
+@pytest.mark.parametrize("k,n,t", [(10, 20, 2), (8, 16, 3), (12, 24, 4), (24, 33, 4), (16, 40, 2), (70, 130, 2)])
+def test_packed_search_equals_the_dense_one_on_tie_rows(k, n, t):
+    rng = np.random.default_rng(200 + n)
+    g = osd_ref.random_full_rank(k, n, rng)
+    llr = osd_ref.tie_rows(n, rng)
+    _assert_packed_equals_dense(g, llr, t, np.ones(len(llr), dtype=bool))
+    # a block boundary inside an order changes nothing
+    a, b = osd_ref.osd_decode_packed(g, llr[:9], t), osd_ref.osd_decode_packed(g, llr[:9], t, block=7)
+    assert all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def test_packed_patterns_are_the_combinations():
+    for k, i in ((5, 1), (6, 3), (9, 4), (4, 4)):
+        p = osd_ref.packed_patterns(k, i)
+        assert p.tolist() == [list(c) for c in itertools.combinations(range(k), i)]
+    assert len(osd_ref.packed_patterns(3, 4)) == 0
+
+
+def test_the_2_22_cap_is_at_k_100_for_order_4():
+    """(100, 104, 4) with 4 087 975 patterns is the largest order-4 search; k = 101 (4 254 726) is refused."""
+    from polar_amd.osd import check_supported
+    assert sum(math.comb(100, i) for i in range(1, 5)) == 4087975 <= 1 << 22 < sum(math.comb(101, i) for i in range(1, 5))
+    check_supported(100, 104, 4)
+    with pytest.raises(ValueError):
+        check_supported(101, 104, 4)
+
+
+def _lane_starts(k, t):
+    """(per, the lane whose first pattern is the first of order i, for i = 2 .. t; None where no lane's is):
+    the kernel gives lane l the patterns l * per .. (l + 1) * per - 1, per = ceil(n_patterns / 64)."""
+    counts = [math.comb(k, i) for i in range(1, t + 1)]
+    per = -(-sum(counts) // 64)
+    starts = np.cumsum(counts)[:-1]
+    return per, [int(s // per) if s % per == 0 else None for s in starts]
+
+
+# What the seeds of osd_ref.ENVELOPE_CASES give: the number of rows won by c0 and by each order 1 .. t.
+# Two cases cannot meet "every order wins somewhere", whatever the input:
+#   * k128n128t2 has no redundant position.  c0 is the hard decision of every position, every a_j is
+#     <= 0 and every Delta >= 0, so c0 wins every row: the case checks the elimination at rate 1, the
+#     search only in that no pattern may win.
+#   * k100n104t4 has four redundant positions.  A pattern J wins only if, for every non-empty R within J,
+#     the redundant positions of the sum of the rows R outweigh the pivots of R (else J without R is at
+#     least as good and comes first).  A redundant position is less reliable than every pivot whose row
+#     reaches it.  Four rows restricted to four positions are dependent, and some R gains nothing, or
+#     a basis, and some R sums to a single position, which does not outweigh R.  So no pattern of order
+#     4 can win at n - k = 4; order 2 is the highest found in a search over seeds, and the order-4
+#     patterns are checked in that 3 921 225 of them must lose.
+ENVELOPE_WINNERS = {
+    "k10n20t2": [80, 34, 10],
+    "k8n16t3": [92, 27, 6, 2],
+    "k12n24t4": [66, 45, 14, 1, 3],
+    "k24n33t4": [66, 46, 15, 1, 1],
+    "k40n200t3": [5, 16, 35, 70],
+    "k66n97t3": [28, 39, 36, 23],
+    "k70n130t2": [12, 46, 66],
+    "k128n128t2": [124, 0, 0],
+    "k16n40t2_structured": [90, 27, 7],
+    "k16n40t2_structured_permuted": [85, 31, 8],
+    "k64n128t4": [0, 1, 0, 2, 1],
+    "k128n256t3": [1, 1, 1, 1],
+    "k100n104t4": [2, 1, 1, 0, 0],
+}
+
+
+@pytest.mark.parametrize("name", list(osd_ref.ENVELOPE_CASES))
+def test_envelope_inputs_meet_their_conditions(name):
+    """The inputs of tests/test_osd_envelope_gpu.py, judged by the restatement alone: which orders win,
+    the margin of every row that is not exact in fp64, the shapes' lane-boundary facts."""
+    g, t, llr, exact = osd_ref.envelope_case(name)
+    k, n = g.shape
+    corner = name in osd_ref.ENVELOPE_CORNERS
+    assert osd_ref.gf2_rank(g) == k
+    assert (len(llr), exact.sum()) == (4, 0) if corner else ((~exact).sum() >= 48 and exact.sum() == 73)
+    cw, dist, pattern, gap = (osd_ref.osd_decode_packed if corner else osd_ref.osd_decode)(g, llr, t)
+    hist = np.bincount(osd_ref.winner_orders(pattern, k, t), minlength=t + 1).tolist()
+    print(name, "rows", len(llr), "winner orders", hist, "min gap", float(gap[~exact].min()))
+    assert hist == ENVELOPE_WINNERS[name]
+    assert gap[~exact].min() > 1e-9
+    if name == "k128n128t2":
+        assert hist[0] == len(llr)
+    elif name == "k100n104t4":
+        assert hist[0] > 0 and hist[1] > 0 and hist[2] > 0
+    elif corner:
+        assert hist[t] > 0
+    else:
+        assert all(h > 0 for h in hist)
+    if name == "k10n20t2":  # per == 1, lanes 55 .. 63 idle, lane 10 starts order 2 and its pattern wins a row
+        assert _lane_starts(k, t) == (1, [10]) and math.comb(10, 1) + math.comb(10, 2) == 55 < 64
+        assert 10 in pattern
+    if name == "k8n16t3":  # per == 2, lane 4 starts order 2 (its pattern wins a row), lane 18 order 3
+        assert _lane_starts(k, t) == (2, [4, 18]) and 8 in pattern
+    if name.startswith("k16n40t2_structured"):
+        cols = {c.tobytes() for c in g.T}
+        assert (g.sum(0) == 0).sum() == 8 and len(cols) == 17  # 8 zero columns, 16 columns repeated
+        dependent = [osd_ref.gf2_rank(g[:, np.argsort(-np.abs(np.clip(r, -100, 100)), kind="stable")[:k]]) < k for r in llr]
+        assert sum(dependent) > len(llr) // 2  # the first k sorted columns do not span: the pivots skip
+    if name in ("k66n97t3", "k70n130t2", "k128n256t3", "k100n104t4"):  # rows past lane 63's first slot take part
+        members = [osd_ref.packed_patterns(k, o)[p - sum(math.comb(k, i) for i in range(1, o))]
+                   for o, p in zip(osd_ref.winner_orders(pattern, k, t), pattern) if o > 0]
+        assert max(int(m.max()) for m in members) > 63

@@ -89,29 +89,7 @@ def test_parity_with_the_reference_and_the_restatement(golden, name):
     assert np.allclose(dist, want_dist, rtol=1e-12, atol=0)
 
 
-def _tie_rows(n, rng):
-    """Rows that exercise the tie policy; all values are multiples of 2^-6 below 2^7, so every Delta
-    is an exact fp64 sum whatever its order."""
-    rows = []
-    for v in (0.5, 3.0, 100.0):  # all-equal |llr|
-        rows += [np.full(n, v) * rng.choice([-1.0, 1.0], n) for _ in range(8)]
-    for _ in range(16):  # clipped to +-100 in half the positions
-        r = np.round(rng.normal(0, 4, n) * 64) / 64
-        half = rng.permutation(n)[: n // 2]
-        r[half] = rng.choice([-1.0, 1.0], n // 2) * rng.choice([100.0, 250.0, 1e6], n // 2)
-        rows.append(r)
-    for _ in range(16):  # exact zeros of either sign: hard decision 0, tie among themselves
-        r = np.round(rng.normal(0, 4, n) * 64) / 64
-        z = rng.permutation(n)[: n // 3]
-        r[z] = rng.choice([0.0, -0.0], z.size)
-        rows.append(r)
-    for _ in range(16):  # +-Inf is clipped like any large value
-        r = np.round(rng.normal(0, 4, n) * 64) / 64
-        z = rng.permutation(n)[: n // 4]
-        r[z] = rng.choice([-np.inf, np.inf], z.size)
-        rows.append(r)
-    rows.append(np.zeros(n))
-    return np.array(rows, dtype=np.float32)
+_tie_rows = osd_ref.tie_rows
 
 
 @pytest.mark.parametrize("k,n,t", [(16, 32, 2), (32, 64, 2), (65, 130, 1)])
