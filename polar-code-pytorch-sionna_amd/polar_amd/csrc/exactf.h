@@ -424,42 +424,24 @@ __device__ const double kTabLogL[512] = {
 };
 // ---- END GENERATED TABLES ----
 
-#ifndef PL_EXF_LEAN
-#define PL_EXF_LEAN 1
-#endif
-// LDS copies of the tables, one per work-group (6 KiB lean, 8 KiB otherwise): every kernel that evaluates the exact f
+// LDS copies of the tables, one per work-group (6 KiB): every kernel that evaluates the exact f
 // calls load_tables() before its first f (all threads of the work-group, then a barrier).
-#if PL_EXF_LEAN
 struct alignas(16) Tabs {
     double e[256];   // kTabExp1
     double cl[512];  // cell j: {c_j, hi(-ln c_j)} side by side, one 16-byte read (6 KiB in all)
 };
-#else
-struct alignas(16) Tabs {
-    double e[256];  // kTabExp
-    double c[256];  // kTabLogC
-    double l[512];  // kTabLogL
-};
-#endif
 __shared__ Tabs tabs;
 
 __device__ __forceinline__ void load_tables(int tid, int nthreads) {
     for (int i = tid; i < 256; i += nthreads) {
-#if PL_EXF_LEAN
         tabs.e[i] = kTabExp1[i];
         tabs.cl[2 * i] = kTabLogC[i];
         tabs.cl[2 * i + 1] = kTabLogL[2 * i];
-#else
-        tabs.e[i] = kTabExp[i];
-        tabs.c[i] = kTabLogC[i];
-        tabs.l[i] = kTabLogL[i];
-        tabs.l[i + 256] = kTabLogL[i + 256];
-#endif
     }
     __syncthreads();
 }
 
-// PL_EXF_LEAN (round 4): exp takes 2^(j/256) as one fp64 value (T + T q, not T_hi + (T_lo + T_hi q)
+// The lean forms (round 4; the 8 KiB two-part tables they replaced left the source): exp takes 2^(j/256) as one fp64 value (T + T q, not T_hi + (T_lo + T_hi q)
 // over 2^(j/128), with a degree-4 instead of a degree-5 polynomial),
 // log drops the low part of -ln c_j, and the f builds e^(xc+yc) from the two exps it evaluates
 // anyway -- e^x e^y e^d, d = fl(xc + yc) - (xc + yc) exact in fp64, e^d = 1 + d + d^2/2 (|d| <=
@@ -467,15 +449,12 @@ __device__ __forceinline__ void load_tables(int tid, int nthreads) {
 // ~2^-53 to ~3 2^-53 relative before the one rounding to fp32; the host harness
 // (tools/micro/exactf_rounding.cpp) finds 0 of 5e7 exp, log and f results changed against
 // correctly rounded ones, as before.
-// e^x in fp64 for fp32 x, |x| <= 200: N = rint(x 128/ln2) by the 1.5 * 2^52 shifter (its low word
-// is N), r = x - N ln2/128 (|r| <= ln2/256, exact to ~2^-60), e^r - 1 = q by a degree-5 Taylor
-// polynomial (remainder < 2^-60), e^x = 2^(N >> 7) T (1 + q), T = 2^((N & 127) / 128) from the
-// table as hi + lo; the one rounding that matters is the final T + T q (~2^-53 relative).
+// e^x in fp64 for fp32 x, |x| <= 200: N = rint(x 256/ln2) by the 1.5 * 2^52 shifter (its low word
+// is N), x = N ln2/256 + r, |r| <= ln2/512: e^r - 1 = q by degree 4 (remainder < 2^-54), T = 2^(j/256)
+// as one fp64 value, e^x = 2^(N >> 8) (T + T q); the one rounding that matters is that final
+// T + T q.
 __device__ __forceinline__ double exp_d(float xf) {
     const double x = (double)xf;
-#if PL_EXF_LEAN
-    // x = N ln2/256 + r, |r| <= ln2/512: e^r - 1 = q by degree 4 (remainder < 2^-54), T = 2^(j/256)
-    // as one fp64 value, e^x = 2^(N >> 8) (T + T q)
     const double t = __builtin_fma(x, kTabInvC1, 0x1.8p52);
     const int n = (int)(uint32_t)__builtin_bit_cast(unsigned long long, t);
     const double nd = t - 0x1.8p52;
@@ -487,42 +466,18 @@ __device__ __forceinline__ double exp_d(float xf) {
     const double q = __builtin_fma(r2, h, r);
     const double th = tabs.e[n & 255];
     return __builtin_ldexp(__builtin_fma(th, q, th), n >> 8);
-#else
-    const double t = __builtin_fma(x, kTabInvC, 0x1.8p52);
-    const int n = (int)(uint32_t)__builtin_bit_cast(unsigned long long, t);
-    const double nd = t - 0x1.8p52;
-    double r = __builtin_fma(-nd, kTabCHi, x);
-    r = __builtin_fma(-nd, kTabCLo, r);
-    const double r2 = r * r;
-    double h = __builtin_fma(1.0 / 120.0, r, 1.0 / 24.0);
-    h = __builtin_fma(h, r, 1.0 / 6.0);
-    h = __builtin_fma(h, r, 0.5);
-    const double q = __builtin_fma(r2, h, r);
-    const int j = n & 127;
-    const double th = tabs.e[2 * j], tl = tabs.e[2 * j + 1];
-    const double m = __builtin_fma(th, q, tl) + th;
-    return __builtin_ldexp(m, n >> 7);
-#endif
 }
 // fp32 exp(x), |x| <= 87, correctly rounded (but for ~2^-28 of the arguments): one rounding of
 // the fp64 value (the 2^k scaling is exact in fp64)
 __device__ __forceinline__ float exp_cr(float xf) { return (float)exp_d(xf); }
 // fp32 e^(fl(xc + yc)) from the fp64 e^xc, e^yc: e^xc e^yc e^d, d = fl(xc + yc) - (xc + yc), which
-// Fast2Sum gives exactly in fp32 ((s - a) - b with |a| >= |b|)
-#ifndef PL_EXF_TWOSUM
-#define PL_EXF_TWOSUM 1  // d by the branch-free TwoSum (5 adds) instead of the ordered Fast2Sum (compare, 2 selects, 2 subs): A/B 0.8155 -> 0.8089 ms, bit-identical (profiles/r05zz_sc_exact_twosum_ab.txt)
-#endif
+// the branch-free TwoSum gives exactly in fp32 (5 adds; the ordered Fast2Sum -- compare, 2 selects,
+// 2 subs -- it replaced: A/B 0.8155 -> 0.8089 ms, bit-identical, profiles/r05zz_sc_exact_twosum_ab.txt)
 __device__ __forceinline__ float exp_sum(double ex, double ey, float xc, float yc) {
     const float s = xc + yc;
-#if PL_EXF_TWOSUM
-    // TwoSum: e = (xc + yc) - s exactly, d = -e; the same exact value as the ordered form
+    // TwoSum: e = (xc + yc) - s exactly, d = -e
     const float bb = s - xc;
     const double d = -(double)((xc - (s - bb)) + (yc - bb));
-#else
-    const bool sw = __builtin_fabsf(yc) > __builtin_fabsf(xc);
-    const float a = sw ? yc : xc, b = sw ? xc : yc;
-    const double d = (double)((s - a) - b);
-#endif
     return (float)(ex * ey * __builtin_fma(d, __builtin_fma(d, 0.5, 1.0), 1.0));
 }
 
@@ -537,12 +492,8 @@ __device__ __forceinline__ double log_d(float xf) {
     const uint32_t mb = (uint32_t)d & 0x7FFFFFu;
     const int j = (int)(mb >> 15);
     const double m = (double)__uint_as_float(mb + kTabLogBase);
-#if PL_EXF_LEAN
     const double2 cl = *reinterpret_cast<const double2*>(&tabs.cl[2 * j]);
     const double r = __builtin_fma(m, cl.x, -1.0);
-#else
-    const double r = __builtin_fma(m, tabs.c[j], -1.0);
-#endif
     const double r2 = r * r;
     double p = __builtin_fma(-1.0 / 6.0, r, 1.0 / 5.0);
     p = __builtin_fma(p, r, -0.25);
@@ -550,13 +501,8 @@ __device__ __forceinline__ double log_d(float xf) {
     p = __builtin_fma(p, r, -0.5);
     const double l1 = __builtin_fma(r2, p, r);
     const double de = (double)e;
-#if PL_EXF_LEAN
     const double hi = __builtin_fma(de, kTabLn2Hi, cl.y);
     const double lo = __builtin_fma(de, kTabLn2Lo, l1);
-#else
-    const double hi = __builtin_fma(de, kTabLn2Hi, tabs.l[2 * j]);
-    const double lo = __builtin_fma(de, kTabLn2Lo, tabs.l[2 * j + 1]) + l1;
-#endif
     return hi + lo;
 }
 __device__ __forceinline__ float log_cr(float xf) { return (float)log_d(xf); }
@@ -610,56 +556,26 @@ __device__ __forceinline__ bool wide_range(float lmax) {
 // clip(x, +-lmax) (dec.py:39-40) as one v_med3_f32 instead of the canonicalising v_max / v_min
 // pairs fminf(fmaxf(x, -lmax), lmax) compiles to (LLRs are never NaN: DESIGN.md section 7); the
 // same value for every other input, +-0 included
-#ifndef PL_EXF_MED3
-#define PL_EXF_MED3 1
-#endif
 __device__ __forceinline__ float clip_l(float x, float lmax) {
-#if PL_EXF_MED3
     return __builtin_amdgcn_fmed3f(x, -lmax, lmax);
-#else
-    return fminf(fmaxf(x, -lmax), lmax);
-#endif
 }
 // the plan's llr_max is the same in every lane: taken as a scalar, the wide-range test is a scalar
 // branch instead of an exec-mask if/else (the out-of-line f receives it in a VGPR)
-#ifndef PL_EXF_UNIFORM
-#define PL_EXF_UNIFORM 1
-#endif
 __device__ __forceinline__ float uniform_l(float lmax) {
-#if PL_EXF_UNIFORM
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lmax)));
-#else
-    return lmax;
-#endif
 }
 
 // f of my_sn/fec/polar/dec.py:39-43 on clipped inputs, each operation rounded as the reference does.
 // Out of line: inlined into the fully unrolled specialised SC kernels (hundreds of f per lane) the
-// fp64 code made one (128,256) kernel take minutes to compile.  PL_EXF_INLINE 1 inlines f_exact and
-// f_exact2 (fixed-range builds only, PL_EXF_RANGE != 0).
-#ifndef PL_EXF_INLINE
-#define PL_EXF_INLINE 0
-#endif
-#if PL_EXF_INLINE && PL_EXF_RANGE == 0
-#error "PL_EXF_INLINE needs PL_EXF_RANGE 1 or 2"
-#endif
-#if PL_EXF_INLINE
-#define PL_EXF_ATTR __attribute__((always_inline))
-#else
-#define PL_EXF_ATTR __attribute__((noinline))
-#endif
-__device__ PL_EXF_ATTR float f_exact(float x, float y, float lmax) {
+// fp64 code made one (128,256) kernel take minutes to compile (inlining f_exact and f_exact2 in
+// the fixed-range builds was not taken either: DESIGN.md, the exact-f section).
+__device__ __attribute__((noinline)) float f_exact(float x, float y, float lmax) {
     lmax = uniform_l(lmax);
     if (wide_range(lmax)) return f_exact_wide(x, y, lmax);
     const float xc = clip_l(x, lmax), yc = clip_l(y, lmax);
-#if PL_EXF_LEAN
     const double ex = exp_d(xc), ey = exp_d(yc);
     float o = log_cr(1.0f + exp_sum(ex, ey, xc, yc));
     o -= log_cr((float)ex + (float)ey);
-#else
-    float o = log_cr(1.0f + exp_cr(xc + yc));
-    o -= log_cr(exp_cr(xc) + exp_cr(yc));
-#endif
     return o;
 }
 
@@ -669,20 +585,14 @@ __device__ PL_EXF_ATTR float f_exact(float x, float y, float lmax) {
 struct f2 {
     float a, b;
 };
-__device__ PL_EXF_ATTR f2 f_exact2(float x0, float y0, float x1, float y1, float lmax) {
+__device__ __attribute__((noinline)) f2 f_exact2(float x0, float y0, float x1, float y1, float lmax) {
     lmax = uniform_l(lmax);
     if (wide_range(lmax)) return f2{f_exact_wide(x0, y0, lmax), f_exact_wide(x1, y1, lmax)};
     const float xc0 = clip_l(x0, lmax), yc0 = clip_l(y0, lmax);
     const float xc1 = clip_l(x1, lmax), yc1 = clip_l(y1, lmax);
-#if PL_EXF_LEAN
     const double ea0 = exp_d(xc0), ea1 = exp_d(xc1), eb0 = exp_d(yc0), eb1 = exp_d(yc1);
     const float s0 = exp_sum(ea0, eb0, xc0, yc0), s1 = exp_sum(ea1, eb1, xc1, yc1);
     const float a0 = (float)ea0, a1 = (float)ea1, b0 = (float)eb0, b1 = (float)eb1;
-#else
-    const float s0 = exp_cr(xc0 + yc0), s1 = exp_cr(xc1 + yc1);
-    const float a0 = exp_cr(xc0), a1 = exp_cr(xc1);
-    const float b0 = exp_cr(yc0), b1 = exp_cr(yc1);
-#endif
     const float p0 = log_cr(1.0f + s0), p1 = log_cr(1.0f + s1);
     const float q0 = log_cr(a0 + b0), q1 = log_cr(a1 + b1);
     f2 r;

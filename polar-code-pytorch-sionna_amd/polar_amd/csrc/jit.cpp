@@ -325,7 +325,7 @@ int attach_static(pl_plan* p, const uint8_t* frozen, bool allow_compile) {
     hipFunction_t f32, u8;
     r = check_hip(hipModuleGetFunction(&f32, mod, "pl_sc_static_f32"), "hipModuleGetFunction");
     if (!r) r = check_hip(hipModuleGetFunction(&u8, mod, "pl_sc_static_u8"), "hipModuleGetFunction");
-    hipFunction_t cnt = nullptr;  // optional (absent from diagnostic builds): decode + error count
+    hipFunction_t cnt = nullptr;  // optional (absent from a development PL_SC_STAMPS build): decode + error count
     if (!r && hipModuleGetFunction(&cnt, mod, "pl_sc_static_cnt") != hipSuccess) {
         cnt = nullptr;
         (void)hipGetLastError();
@@ -354,34 +354,24 @@ int attach_static(pl_plan* p, const uint8_t* frozen, bool allow_compile) {
         (void)hipModuleUnload(mod);
         return r;
     }
-    // persistent kernels get a grid of the resident capacity (2 blocks of 4 waves per CU)
+    // waves per work-group: the layout the code object was built with (sc_static.h PL_SC_KWAVES)
     hipDeviceptr_t gp = nullptr;
     size_t gsz = 0;
-    int persistent = 0;
-    if (hipModuleGetGlobal(&gp, &gsz, mod, "pl_sc_persistent") == hipSuccess && gsz == sizeof(int))
-        (void)hipMemcpyDtoH(&persistent, gp, sizeof(int));
-    (void)hipGetLastError();
-    int bpc = 2;  // resident blocks per CU of a persistent kernel (pl_sc_blocks_per_cu, default 2)
-    if (persistent && hipModuleGetGlobal(&gp, &gsz, mod, "pl_sc_blocks_per_cu") == hipSuccess && gsz == sizeof(int))
-        (void)hipMemcpyDtoH(&bpc, gp, sizeof(int));
-    (void)hipGetLastError();
-    if (bpc < 1) bpc = 1;
-    int waves = 4;  // waves per work-group (pl_sc_waves; objects built before it existed: 4)
-    if (hipModuleGetGlobal(&gp, &gsz, mod, "pl_sc_waves") == hipSuccess && gsz == sizeof(int))
-        (void)hipMemcpyDtoH(&waves, gp, sizeof(int));
-    (void)hipGetLastError();
+    int waves = 0;
+    if (hipModuleGetGlobal(&gp, &gsz, mod, "pl_sc_waves") != hipSuccess || gsz != sizeof(int) ||
+        hipMemcpyDtoH(&waves, gp, sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(mod);
+        set_error("specialised SC kernel: the code object does not say its waves per work-group (pl_sc_waves)");
+        return PL_EINVAL;
+    }
     if (waves != 1 && waves != 2 && waves != 4) {
         (void)hipModuleUnload(mod);
         set_error("specialised SC kernel: unsupported waves per work-group");
         return PL_EINVAL;
     }
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     p->sc_log_g = lg;
     p->sc_waves = waves;
-    p->sc_persistent = persistent;
-    p->resident_blocks = bpc * cus;
     p->sc_module = mod;
     p->sc_fn_f32 = f32;
     p->sc_fn_u8 = u8;
@@ -405,10 +395,6 @@ int64_t sc_count_waves(const pl_plan* p, int64_t bs) {
 int launch_sc_static_count(const pl_plan* p, const float* llr, int64_t bs, const uint32_t* ref, int32_t* part,
                            hipStream_t st) {
     if (bs == 0 || p->k == 0) return PL_OK;
-    if (p->sc_persistent) {
-        set_error("SC decode+count: the plan's kernel is a persistent diagnostic build");
-        return PL_ENOTSUP;
-    }
     const int64_t blocks = sc_count_waves(p, bs) / p->sc_waves;
     if (blocks > 0x7fffffffLL) {
         set_error("SC decode+count: batch too large for one launch");
@@ -444,8 +430,7 @@ int launch_sc_static(const pl_plan* p, const float* llr, int64_t bs, void* out, 
     if (bs == 0 || p->k == 0) return PL_OK;
     const int G = 1 << p->sc_log_g;           // the layout the plan's kernel was built for
     const int64_t per_block = p->sc_waves * (64 / G);  // pls::kWaves codeword groups of 64/G
-    int64_t blocks = (bs + per_block - 1) / per_block;
-    if (p->sc_persistent && p->resident_blocks > 0 && blocks > p->resident_blocks) blocks = p->resident_blocks;
+    const int64_t blocks = (bs + per_block - 1) / per_block;
     if (blocks > 0x7fffffffLL) {
         set_error("SC decode: batch too large for one launch");
         return PL_EINVAL;

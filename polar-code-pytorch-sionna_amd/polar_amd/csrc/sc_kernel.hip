@@ -36,34 +36,12 @@
 
 namespace {
 
-#ifndef PL_SC_SHORTCUTS
-#define PL_SC_SHORTCUTS 13  // bit 0 rep, bit 1 rate-1, bit 2 SPC, bit 3 skip-f of rate-0 left children
-#endif
-constexpr int kShortcuts = PL_SC_SHORTCUTS;
-#ifndef PL_SC_MIN_WAVES
-#define PL_SC_MIN_WAVES 2  // waves per SIMD the register allocation must allow (occupancy target)
-#endif
-#ifndef PL_SC_SHORTCUT_MAX_E
-#define PL_SC_SHORTCUT_MAX_E 8  // shortcuts only on nodes with <= this many elements per lane
-#endif
-#ifndef PL_SC_ROOT_STORED
-#define PL_SC_ROOT_STORED 0  // 1: hold stage n/2 in VGPRs; 0: recompute it from the channel
-#endif
-#ifndef PL_SC_CH_REGS
-#define PL_SC_CH_REGS 0  // 1: load this lane's n/G channel values into VGPRs once at the root
-#endif
-#ifndef PL_SC_LAUNDER_CH
-#define PL_SC_LAUNDER_CH 0  // 1: re-load the channel from L2 per pass instead of holding it in VGPRs
-#endif
-#ifndef PL_SC_DPP_GATHER
-#define PL_SC_DPP_GATHER 1  // gather a G-node's LLRs with DPP (VALU) instead of ds_bpermute
-#endif
-#ifndef PL_SC_LAUNDER_BL
-#define PL_SC_LAUNDER_BL 0
-#endif
-#ifndef PL_SC_ROOT_CHUNK
-#define PL_SC_ROOT_CHUNK 8  // root f/g outputs per scheduling chunk (bounds loads in flight)
-#endif
+// Shortcuts compiled in: repetition, SPC, and skipping the f pass of a rate-0 left child.  The
+// rate-1 shortcut is not: alone it slightly hurts, these codes have few rate-1 nodes.
+constexpr int kMinWaves = 2;      // waves per SIMD the register allocation must allow (occupancy target)
+constexpr int kShortcutMaxE = 8;  // shortcuts only on nodes with <= this many elements per lane
+constexpr int kRootChunk = 8;     // root f/g outputs per scheduling chunk (bounds loads in flight)
+constexpr int kLoopDepth = 3;     // nodes with >= 2^depth elements per lane run their children in a loop
 constexpr int kWavesPerBlock = 4;
 #ifndef PL_SC_DIAG_SAMEROW
 #define PL_SC_DIAG_SAMEROW 0  // diagnostic builds only (tools/variants.py)
@@ -74,10 +52,6 @@ constexpr int kWavesPerBlock = 4;
 #if !PL_DEV && (PL_SC_DIAG_SAMEROW || PL_SC_DIAG_NOSTORE)
 #error "PL_SC_DIAG_* macros give wrong results: development builds (-DPL_DEV=1) only"
 #endif
-#ifndef PL_SC_LOOP_DEPTH
-#define PL_SC_LOOP_DEPTH 3  // nodes with >= 2^depth elements per lane run their children in a loop
-#endif
-constexpr int kLoopDepth = PL_SC_LOOP_DEPTH;
 
 template <int E>
 using BetaT = typename std::conditional<(E <= 32), uint32_t, uint64_t>::type;
@@ -283,7 +257,7 @@ __device__ __forceinline__ uint32_t inl(const float (&v)[1 << t], uint32_t fw, f
 // v[j] = LLR held by lane j of this lane's group (all G of them, in every lane).
 template <int G>
 __device__ __forceinline__ void gather(float a, const Ctx& c, float (&v)[G]) {
-#if PL_SC_DPP_GATHER
+    // DPP (VALU) for G <= 8 instead of ds_bpermute; G = 16 takes the __shfl tail
     if constexpr (G == 2) {
         v[0] = dppf<0xA0>(a);  // quad_perm [0,0,2,2]
         v[1] = dppf<0xF5>(a);  // quad_perm [1,1,3,3]
@@ -310,7 +284,6 @@ __device__ __forceinline__ void gather(float a, const Ctx& c, float (&v)[G]) {
         }
         return;
     }
-#endif
     const int base = c.lane & ~(G - 1);
 #pragma unroll
     for (int j = 0; j < G; ++j) v[j] = __shfl(a, base + j, 64);
@@ -326,10 +299,9 @@ __device__ __forceinline__ uint32_t bottom(float a, int p, const Ctx& c) {
         const int ty = node_type<LOG_N, LOG_G>(c, p);
         if (ty == T_R0) return 0u;
         const float av[1] = {a};
-        if ((kShortcuts & 1) && ty == T_REP) return rep_node<G, 1>(av, c);
+        if (ty == T_REP) return rep_node<G, 1>(av, c);
         if constexpr (FM == 0) {
-            if ((kShortcuts & 2) && ty == T_R1 && !__any(a == 0.0f)) return hd(a);
-            if ((kShortcuts & 4) && ty == T_SPC) {
+            if (ty == T_SPC) {
                 uint32_t b;
                 if (spc_node<G, 1>(av, c, b)) return b;
             }
@@ -373,7 +345,7 @@ __device__ __forceinline__ BetaT<(1 << (s - LOG_G))> split(const float (&a)[1 <<
     using BH = BetaT<H>;
     float x[H];
     BH bl = 0, br = 0;
-    const bool left_r0 = (kShortcuts & 8) && child_r0<LOG_N, s - 1>(c, p);
+    const bool left_r0 = child_r0<LOG_N, s - 1>(c, p);
     if constexpr (E >= (1 << kLoopDepth)) {
 #pragma unroll 1
         for (int side = left_r0 ? 1 : 0; side < 2; ++side) {
@@ -405,13 +377,12 @@ template <int LOG_N, int LOG_G, int s, int FM>
 __device__ __forceinline__ BetaT<(1 << (s - LOG_G))> node(const float (&a)[1 << (s - LOG_G)], int p, const Ctx& c) {
     constexpr int E = 1 << (s - LOG_G), G = 1 << LOG_G;
     using BT = BetaT<E>;
-    if constexpr (E <= PL_SC_SHORTCUT_MAX_E) {
+    if constexpr (E <= kShortcutMaxE) {
         const int ty = node_type<LOG_N, s>(c, p);
         if (ty == T_R0) return (BT)0;
-        if ((kShortcuts & 1) && ty == T_REP) return rep_node<G, E>(a, c);
+        if (ty == T_REP) return rep_node<G, E>(a, c);
         if constexpr (FM == 0) {
-            if ((kShortcuts & 2) && ty == T_R1 && !__any(any_zero<E>(a))) return hd_bits<E>(a);
-            if ((kShortcuts & 4) && ty == T_SPC) {
+            if (ty == T_SPC) {
                 BT b;
                 if (spc_node<G, E>(a, c, b)) return b;
             }
@@ -462,41 +433,6 @@ __device__ __forceinline__ float root_alpha(const float* __restrict__ chl, const
 }
 
 template <int LOG_N, int LOG_G, int FM>
-__device__ __forceinline__ float root_alpha_r(const float (&chv)[(1 << LOG_N) >> LOG_G], const Ctx& c, int side,
-                                              uint64_t bl_root, int j) {
-    constexpr int NS = (1 << LOG_N) >> LOG_G;
-    const float x = -chv[j], y = -chv[j + NS / 2];
-    return side == 0 ? fop<FM>(x, y, c.lmax) : gop(x, y, bitof(bl_root, j));
-}
-
-template <int LOG_N, int LOG_G, int FM>
-__device__ __forceinline__ BetaT<((1 << LOG_N) >> LOG_G) / 2> half_node_r(const float (&chv)[(1 << LOG_N) >> LOG_G],
-                                                                          const Ctx& c, int side, uint64_t bl_root) {
-    constexpr int s = LOG_N - 1, E = (1 << s) >> LOG_G, H = E / 2, h = 1 << (s - 1);
-    using BT = BetaT<E>;
-    using BH = BetaT<H>;
-    const int p = side * (1 << s);
-    if (is_r0<LOG_N, s>(c, p)) return (BT)0;
-    float x[H];
-    BH bl = 0, br = 0;
-    const bool left_r0 = (kShortcuts & 8) && child_r0<LOG_N, s - 1>(c, p);
-#pragma unroll 1
-    for (int sd = left_r0 ? 1 : 0; sd < 2; ++sd) {
-        uint64_t blr = bl_root;
-        asm volatile("" : "+v"(blr));
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-            const float a0 = root_alpha_r<LOG_N, LOG_G, FM>(chv, c, side, blr, j);
-            const float a1 = root_alpha_r<LOG_N, LOG_G, FM>(chv, c, side, blr, j + H);
-            x[j] = sd == 0 ? fop<FM>(a0, a1, c.lmax) : gop(a0, a1, bitof(bl, j));
-        }
-        const BH b = child<LOG_N, LOG_G, s - 1, FM>(x, p + sd * h, c);
-        if (sd == 0) bl = b; else br = b;
-    }
-    return (BT)(bl ^ br) | ((BT)br << H);
-}
-
-template <int LOG_N, int LOG_G, int FM>
 __device__ __forceinline__ BetaT<((1 << LOG_N) >> LOG_G) / 2> half_node(const float* __restrict__ ch, const Ctx& c,
                                                                         int side, uint64_t bl_root) {
     constexpr int s = LOG_N - 1, E = (1 << s) >> LOG_G, H = E / 2, h = 1 << (s - 1);
@@ -506,28 +442,18 @@ __device__ __forceinline__ BetaT<((1 << LOG_N) >> LOG_G) / 2> half_node(const fl
     if (is_r0<LOG_N, s>(c, p)) return (BT)0;
     float x[H];
     BH bl = 0, br = 0;
-    const bool left_r0 = (kShortcuts & 8) && child_r0<LOG_N, s - 1>(c, p);
-    constexpr int CH = PL_SC_ROOT_CHUNK < H ? PL_SC_ROOT_CHUNK : H;
+    const bool left_r0 = child_r0<LOG_N, s - 1>(c, p);
+    constexpr int CH = kRootChunk < H ? kRootChunk : H;
 #pragma unroll 1
     for (int sd = left_r0 ? 1 : 0; sd < 2; ++sd) {
-        // Launder the channel pointer per pass: the loads are loop-invariant, and LICM would
-        // otherwise hoist all of them and keep the whole stage in VGPRs (the thing avoided here).
+        // The loads are loop-invariant: LICM hoists them, so the channel stays in VGPRs (one HBM
+        // pass; laundering the pointer per pass to re-load it from L2 is not taken).
 #pragma unroll
         for (int j0 = 0; j0 < H; j0 += CH) {
-#if PL_SC_LAUNDER_CH
-            const float* chp = ch;
-            asm volatile("" : "+v"(chp));
-#else
-            const float* chp = ch;  // loads hoisted by LICM: the channel stays in VGPRs (one HBM pass)
-#endif
-            uint64_t blr = bl_root;
-#if PL_SC_LAUNDER_BL
-            asm volatile("" : "+v"(blr));  // keeps LICM from hoisting its 2H sign masks into VGPRs
-#endif
 #pragma unroll
             for (int j = j0; j < j0 + CH; ++j) {
-                const float a0 = root_alpha<LOG_N, LOG_G, FM>(chp, c, side, blr, j);
-                const float a1 = root_alpha<LOG_N, LOG_G, FM>(chp, c, side, blr, j + H);
+                const float a0 = root_alpha<LOG_N, LOG_G, FM>(ch, c, side, bl_root, j);
+                const float a1 = root_alpha<LOG_N, LOG_G, FM>(ch, c, side, bl_root, j + H);
                 x[j] = sd == 0 ? fop<FM>(a0, a1, c.lmax) : gop(a0, a1, bitof(bl, j));
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -549,45 +475,10 @@ __device__ __forceinline__ void root(const float* __restrict__ ch, const Ctx& c,
         const float x = -ch[c.lig], y = -ch[c.lig + N / 2];
         bl = bottom<LOG_N, LOG_G, FM>(fop<FM>(x, y, c.lmax), 0, c);
         br = bottom<LOG_N, LOG_G, FM>(gop(x, y, bl), N / 2, c);
-    } else if constexpr (PL_SC_CH_REGS) {
-        constexpr int NS = N / G;
-        float chv[NS];
-#pragma unroll
-        for (int j = 0; j < NS / 2; ++j) {
-            chv[j] = ch[j * G + c.lig];
-            chv[j + NS / 2] = ch[j * G + c.lig + N / 2];
-        }
-#pragma unroll 1
-        for (int side = 0; side < 2; ++side) {
-            const BH b = half_node_r<LOG_N, LOG_G, FM>(chv, c, side, (uint64_t)bl);
-            if (side == 0) bl = b; else br = b;
-        }
-    } else if constexpr (PL_SC_ROOT_STORED) {
-        // stage LOG_N-1 held in VGPRs: the channel is read once per half (two HBM/L2 passes)
-        float a[H];
-        constexpr int CH = PL_SC_ROOT_CHUNK < H ? PL_SC_ROOT_CHUNK : H;
-#pragma unroll 1
-        for (int side = 0; side < 2; ++side) {
-#pragma unroll
-            for (int j0 = 0; j0 < H; j0 += CH) {
-                const float* chp = ch;
-                uint64_t blr = (uint64_t)bl;
-                asm volatile("" : "+v"(chp), "+v"(blr));
-#pragma unroll
-                for (int j = j0; j < j0 + CH; ++j) a[j] = root_alpha<LOG_N, LOG_G, FM>(chp, c, side, blr, j);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const BH b = child<LOG_N, LOG_G, LOG_N - 1, FM>(a, side * (N / 2), c);
-            if (side == 0) bl = b; else br = b;
-        }
     } else {
 #pragma unroll 1
         for (int side = 0; side < 2; ++side) {
-            const float* chp = ch;
-#if PL_SC_LAUNDER_CH
-            asm volatile("" : "+v"(chp));
-#endif
-            const BH b = half_node<LOG_N, LOG_G, FM>(chp, c, side, (uint64_t)bl);
+            const BH b = half_node<LOG_N, LOG_G, FM>(ch, c, side, (uint64_t)bl);
             if (side == 0) bl = b; else br = b;
         }
     }
@@ -602,7 +493,7 @@ __device__ __forceinline__ void root(const float* __restrict__ ch, const Ctx& c,
 }
 
 template <int LOG_N, int FM, int OUTK>
-__global__ __launch_bounds__(64 * kWavesPerBlock, PL_SC_MIN_WAVES) void sc_decode_kernel(
+__global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void sc_decode_kernel(
     const float* __restrict__ llr, int64_t bs, void* __restrict__ out, const uint32_t* __restrict__ frozen_words,
     const uint32_t* __restrict__ type_words, int type_stride, const int32_t* __restrict__ info_pos, int k,
     float lmax) {

@@ -34,6 +34,65 @@
 // When a precondition fails anywhere in the wave the node is decoded by the full recursion.
 #ifndef PL_SC_STATIC_H
 #define PL_SC_STATIC_H
+// ---- Build parameters: every macro this header reads, with its default ---------------------
+// (a) Per-code parameters: jit.cpp static_source writes them in front of this header.
+#ifndef PL_SC_MINW
+#define PL_SC_MINW 2  // waves per SIMD the register allocation must allow (__launch_bounds__)
+#endif
+#ifndef PL_SC_F_BITOP3
+// 1: the min-sum f merges its sign with an explicit v_bitop3.  Slower at n/128 lanes per codeword
+// (+3 ... +13 % at G = 8), hence this default; faster at n/64 lanes (G = 16: 0.1087
+// vs 0.1144 ms), so jit.cpp builds the tuned_wide codes -- min-sum n = 256 ... 1024, the bench
+// kernel among them -- with 1.
+#define PL_SC_F_BITOP3 0
+#endif
+#ifndef PL_SC_ROOT_MODE
+#define PL_SC_ROOT_MODE 0  // 1: stage n/2 held in VGPRs, the channel read once per half (exact-f codes, n >= 128)
+#endif
+#ifndef PL_SC_FLANE_INLINE
+#define PL_SC_FLANE_INLINE 0  // 1: the lane-level exact f inlined (f_lane_exact; needs PL_EXF_RANGE 1 or 2)
+#endif
+#ifndef PL_SC_SIM
+#define PL_SC_SIM 0  // 1: also emit the fused Monte-Carlo entry pl_sc_static_sim (codes with 64 slots per lane)
+#endif
+#ifndef PL_EXF_RANGE
+#define PL_EXF_RANGE 0  // exactf.h: 0 = each f tests llr_max, 1 = llr_max <= 43 only, 2 = the full-range forms only
+#endif
+// (b) Layout: waves per work-group (the launcher reads it back from the code object, pl_sc_waves).
+// One-wave work-groups: a wave's slot and its 8 KiB of LDS are refilled as soon as it retires,
+// instead of when the slowest of its work-group's four waves does (the waves of a SIMD finish
+// up to 1.5x apart).  Same-process A/B (profiles/r02zu_sc_ab_waves.txt, r02zv_*): (512,1024)
+// 0.0813 / 0.0807 vs 0.0817 / 0.0815 ms, (128,256) bs = 4096 0.0078 vs 0.0079 ms.
+#ifndef PL_SC_KWAVES
+#define PL_SC_KWAVES 1
+#endif
+// (c) Development only (jit.cpp marks a PL_DEV library's sources with PL_DEV; tools/ pass
+// -DPL_DEV=1).  The PL_SC_DIAG_* are timing ablations with WRONG results.  PL_SC_STAMPS writes
+// eight 64-bit clock stamps per wave past the bs * k floats of the output buffer, which only
+// tools/static_probe.py allocates.
+#ifndef PL_SC_DIAG_SKIP_LANE
+#define PL_SC_DIAG_SKIP_LANE 0  // the top lane-level nodes decided by their sign: timing without the lane-level subtrees
+#endif
+#ifndef PL_SC_DIAG_NO_LOAD
+#define PL_SC_DIAG_NO_LOAD 0  // synthetic channel values: the tree without the channel loads
+#endif
+#ifndef PL_SC_DIAG_NO_TREE
+#define PL_SC_DIAG_NO_TREE 0  // loads and output without the tree
+#endif
+#ifndef PL_SC_DIAG_SKIP_SPECIAL
+#define PL_SC_DIAG_SKIP_SPECIAL 0  // in-lane REP / SPC / rate-1 nodes decided by their signs
+#endif
+#ifndef PL_SC_STAMPS
+#define PL_SC_STAMPS 0  // per-wave s_memtime / s_memrealtime / HW_ID stamps (f32 entry only)
+#endif
+#if !defined(PL_DEV) && (PL_SC_DIAG_SKIP_LANE || PL_SC_DIAG_NO_LOAD || PL_SC_DIAG_NO_TREE || PL_SC_DIAG_SKIP_SPECIAL || PL_SC_STAMPS)
+#error "PL_SC_DIAG_* give wrong results, PL_SC_STAMPS writes past the output rows: development builds (PL_DEV) only"
+#endif
+#if PL_SC_FLANE_INLINE && PL_EXF_RANGE == 0
+#error "PL_SC_FLANE_INLINE needs PL_EXF_RANGE 1 or 2"
+#endif
+// ---- end of the build parameters -----------------------------------------------------------
+
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,91 +106,10 @@ typedef unsigned long uintptr_t;
 #endif
 #include "exactf.h"  // build.py inlines it into the embedded source
 
-// Tuning macros (overridable per build; development libraries, -DPL_DEV=1, take A/B overrides from jit.cpp)
-#ifndef PL_SC_F_BITOP3
-#define PL_SC_F_BITOP3 0  // A/B on MI355X: 1 (explicit v_bitop3 sign merge) was slower
-#endif
-#ifndef PL_SC_F_BOUNDED
-#define PL_SC_F_BOUNDED 1  // min-sum f of a left child (inputs are f outputs, |x|, |y| <= llr_max) as one med3
-#endif
-#ifndef PL_SC_LANE31
-#define PL_SC_LANE31 1  // lane-level partial sums as bit-31-only flags (one-op hard decision, bitop3 combines)
-#endif
-#ifndef PL_SC_EMIT_PRE
-#define PL_SC_EMIT_PRE 1  // preload the output table entries at kernel start (8 VGPRs)
-#endif
-#ifndef PL_SC_BIT31_ASM
-#define PL_SC_BIT31_ASM 0  // 1: opaque shift (no v_mul_lo fusion); measured slower overall
-#endif
-#ifndef PL_SC_SPC_BALLOT
-#define PL_SC_SPC_BALLOT 0  // 1: SALU ballot uniqueness test instead of a DPP count; measured slower
-#endif
-#ifndef PL_SC_HD_SUB
-#define PL_SC_HD_SUB 1  // leaf decisions as one fp32 subtract of the smallest denormal
-#endif
-#ifndef PL_SC_VA_RECOMPUTE
-#define PL_SC_VA_RECOMPUTE 0  // 1: recompute the left virtual LLRs for the g pass (-32 VGPRs); measured slower
-#endif
-#ifndef PL_SC_CH_LDS
-#define PL_SC_CH_LDS 1  // the upper half of the channel slots lives in LDS (LDS-DMA), not VGPRs (see Ch)
-#endif
-#ifndef PL_SC_DMA_ASM
-#define PL_SC_DMA_ASM 1  // LDS-DMA of the channel half in the saddr form (inline asm)
-#endif
-#ifndef PL_SC_NT
-#define PL_SC_NT 2  // non-temporal hints: bit 0 channel loads, bit 1 output stores (see st_out4)
-#endif
-#ifndef PL_SC_WIDE
-#define PL_SC_WIDE 16  // in-lane partial sums of nodes with <= this many slots per lane: one word per slot
-#endif
-#ifndef PL_SC_PK_G
-#define PL_SC_PK_G 1  // in-lane g adds in pairs (v_pk_add_f32)
-#endif
-#ifndef PL_SC_ROOT_MODE
-#define PL_SC_ROOT_MODE 0
-#endif
-#ifndef PL_SC_MINW
-#define PL_SC_MINW 2
-#endif
-#ifndef PL_SC_STAMPS
-#define PL_SC_STAMPS 0
-#endif
-#ifndef PL_SC_DIAG_SKIP_LANE
-#define PL_SC_DIAG_SKIP_LANE 0
-#endif
-#ifndef PL_SC_DIAG_NO_LOAD
-#define PL_SC_DIAG_NO_LOAD 0
-#endif
-#ifndef PL_SC_DIAG_NO_TREE
-#define PL_SC_DIAG_NO_TREE 0
-#endif
-#ifndef PL_SC_DIAG_SKIP_SPECIAL
-#define PL_SC_DIAG_SKIP_SPECIAL 0
-#endif
-// Diagnostic macros (timing ablations with WRONG results) exist only in development builds
-// (jit.cpp marks a PL_DEV library's sources with PL_DEV).
-#if !defined(PL_DEV) && (PL_SC_DIAG_SKIP_LANE || PL_SC_DIAG_NO_LOAD || PL_SC_DIAG_NO_TREE || PL_SC_DIAG_SKIP_SPECIAL)
-#error "PL_SC_DIAG_* macros give wrong results: development builds (PL_DEV) only"
-#endif
-#ifndef PL_SC_PERSIST
-#define PL_SC_PERSIST 0  // 1: persistent software-pipelined waves (grid = resident waves)
-#endif
-// PL_SC_PERSIST 2: persistent waves whose next batch of channel rows is staged in LDS by an
-// asynchronous global->LDS copy (global_load_lds_dwordx4) while the current batch is decoded:
-// no channel-load latency on the critical path, 2 waves/SIMD (the staging takes 16 KiB of LDS
-// per wave at n = 1024).  Needs N >= 256 (whole 1-KiB copies per row).
-
 namespace pls {
 
 enum : int { R0 = 0, R1 = 1, REP = 2, SPC = 3, GEN = 4 };
 enum : int { OUT_F32 = 0, OUT_U8 = 1, OUT_CNT = 2, OUT_SIM = 3 };
-#ifndef PL_SC_KWAVES
-// One-wave work-groups: a wave's slot and its 8 KiB of LDS are refilled as soon as it retires,
-// instead of when the slowest of its work-group's four waves does (the waves of a SIMD finish
-// up to 1.5x apart).  Same-process A/B (profiles/r02zu_sc_ab_waves.txt, r02zv_*): (512,1024)
-// 0.0813 / 0.0807 vs 0.0817 / 0.0815 ms, (128,256) bs = 4096 0.0078 vs 0.0079 ms.
-#define PL_SC_KWAVES 1
-#endif
 constexpr int kWaves = PL_SC_KWAVES;  // waves per workgroup (the launcher reads pl_sc_waves)
 
 template <bool B, class T, class F>
@@ -145,14 +123,15 @@ struct Cond<false, T, F> {
 template <int E>
 using Beta = typename Cond<(E <= 32), uint32_t, uint64_t>::type;
 
-// PL_SC_CH_LDS applies to n = 1024 at 16 lanes per codeword (64 channel slots per lane): 8 KiB of
+// CHL: the upper half of the channel slots lives in LDS (LDS-DMA), not in VGPRs.  At n = 1024 with
+// 16 lanes per codeword (64 channel slots per lane): 8 KiB of
 // LDS per wave, 32 KiB per block, so four blocks fit a CU's 160 KiB, and the 32 VGPRs saved
 // (133 -> 103) lift the kernel from three to four waves per SIMD: 0.0854 vs 0.0882 ms at
 // (512,1024), bs = 65536 (profiles/r02s_sc_ab_ch_lds.txt).  At n = 64 ... 512 the kernel already
 // ran at that occupancy and the LDS round trip only costs (+4 ... +39 %), so they keep VGPRs.
 template <class C>
 struct Ch {
-    static constexpr int CHL = (PL_SC_CH_LDS && C::NS == 64 && C::LOG_N == 10) ? 1 : 0;
+    static constexpr int CHL = (C::NS == 64 && C::LOG_N == 10) ? 1 : 0;
 };
 
 template <class C>
@@ -174,26 +153,16 @@ __device__ __forceinline__ Beta<E> ones() {
 __device__ __forceinline__ uint32_t fu(float x) { return __float_as_uint(x); }
 __device__ __forceinline__ float uf(uint32_t x) { return __uint_as_float(x); }
 
-// Output rows are written once: with the non-temporal hint (PL_SC_NT bit 1) they do not push
+// Output rows are written once: with the non-temporal hint they do not push
 // the channel rows out of L2 / the Infinity Cache.  Measured with every launch streaming a batch
 // the Infinity Cache does not hold (sc_ab.py --rotate 3): 0.0809 vs 0.0841 ms; non-temporal channel
-// loads (bit 0) were slower here (0.0875 ms) although a load/store-only kernel of the same shapes
+// loads were slower here (0.0875 ms, profiles/r02u_sc_ab_nontemporal.txt: the channel loads are
+// plain) although a load/store-only kernel of the same shapes
 // gains with both hints (5.78 vs 5.38 TB/s, tools/micro/load_pattern.hip).
-__device__ __forceinline__ float ld_ch(const float* p) {
-#if PL_SC_NT & 1
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
 typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_out4(float* p, float4 v) {
-#if PL_SC_NT & 2
     const f4v w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, reinterpret_cast<f4v*>(p));
-#else
-    *reinterpret_cast<float4*>(p) = v;
-#endif
 }
 
 // Mirror inside aligned blocks of S lanes: lane q reads lane q ^ (S-1).  One DPP op.
@@ -221,9 +190,7 @@ __device__ __forceinline__ float flip31(float x, uint32_t t);
 template <int FM, bool BND = false>
 __device__ __forceinline__ float fop(float x, float y, float lmax) {
     if constexpr (FM == 0) {
-#if PL_SC_F_BOUNDED
         if constexpr (BND) return __builtin_amdgcn_fmed3f(-fabsf(x), flip31(y, fu(x)), fabsf(x));
-#endif
         const float m = fminf(fminf(fabsf(x), fabsf(y)), lmax);
 #if PL_SC_F_BITOP3
         // m | ((x ^ y) & sign): v_min3 + v_xor + v_bitop3 ((S0 & S1) | S2, table 0xEA)
@@ -237,19 +204,9 @@ __device__ __forceinline__ float fop(float x, float y, float lmax) {
 }
 // x[j] = f(a[j], a[j + H]), j < H.  Exact f: element pairs through plx::f_exact2 (half the
 // calls, two interleaved evaluations per call).
-#ifndef PL_SC_FEX_PAIR
-#define PL_SC_FEX_PAIR 1
-#endif
-#ifndef PL_SC_FEX_LANE
-#define PL_SC_FEX_LANE 1  // exact f of lane-level nodes split over the lanes holding the pair (f_lane_exact)
-#endif
-#ifndef PL_SC_G_NODPP
-#define PL_SC_G_NODPP 0  // 1: lane-level g as two flips and a plain add, no DPP read of a fresh value and
-                         // no hazard s_nop (A/B r04zl, (512,1024): 1.3 % slower)
-#endif
 template <int FM, bool BND, int H>
 __device__ __forceinline__ void fvec(const float* a, float* x, float lmax) {
-    if constexpr (FM == 1 && H >= 2 && PL_SC_FEX_PAIR) {
+    if constexpr (FM == 1 && H >= 2) {
 #pragma unroll
         for (int j = 0; j < H; j += 2) {
             const plx::f2 r = plx::f_exact2(a[j], a[j + H], a[j + 1], a[j + 1 + H], lmax);
@@ -268,54 +225,37 @@ __device__ __forceinline__ float flip31(float x, uint32_t t) {
 }
 __device__ __forceinline__ float gop(float x, float y, uint32_t t) { return flip31(x, t) + y; }
 // bit j of packed partial sums w moved to bit 31 with one shift (lower bits are don't-care for
-// flip31); j is a compile-time constant after unrolling
+// flip31); j is a compile-time constant after unrolling.  (Kept opaque as one v_lshlrev -- LLVM
+// fuses the shifts into v_mul_lo, only bit 31 being demanded -- it measured slower overall.)
 template <typename W>
 __device__ __forceinline__ uint32_t bit31(W w, int j) {
     uint32_t t = j <= 31 ? (uint32_t)(w << (31 - j)) : (uint32_t)(w >> (j - 31));
-#if PL_SC_BIT31_ASM
-    asm("" : "+v"(t));  // keep it one v_lshlrev (only bit 31 is demanded: LLVM would fuse shifts into v_mul_lo)
-#endif
     return t;
 }
 // hard decision of a leaf, u = 1 iff !(llr > 0) (polar_sc.py:94-97), as a bit-31 flag.
-// PL_SC_LANE31: only bit 31 of a lane-level flag is meaningful (its consumers mask with the
-// lo31 lane masks or shift by 31), so the decision is one arithmetic op, no compare, no VCC.
-// PL_SC_HD_SUB=0 form: one saturating subtract on the bit pattern -- bits(x) - 1 is negative iff
-// bits(x) <= 0 as a signed integer, i.e. x <= +0 or x < 0 (no NaN), and the saturation keeps -0
-// (INT_MIN) negative.  The default form is a plain fp32 subtract, which issues faster on gfx950
-// (tools/micro/issue_cost*.hip: v_add_f32 ~1.1 ns, v_add_i32 clamp ~1.8 ns per wave-instruction).
-#if PL_SC_LANE31 && PL_SC_HD_SUB
+// Only bit 31 of a lane-level flag is meaningful (its consumers mask with the
+// lo31 lane masks or shift by 31), so the decision is one arithmetic op, no compare, no VCC
+// (profiles/r02c_sc_ab_lane31_bounded.txt): a plain fp32 subtract, which issues faster on gfx950
+// than the saturating integer subtract bits(x) - 1 it replaced (profiles/r02r_sc_ab_wide.txt;
+// tools/micro/issue_cost*.hip: v_add_f32 ~1.1 ns, v_add_i32 clamp ~1.8 ns per wave-instruction).
 // x - 2^-149 (the smallest denormal) is negative exactly when x <= 0: +0 and -0 give -2^-149,
 // x = 2^-149 gives +0 (an exact zero rounds to +0), larger x stay positive.  Needs fp32 denormals
 // preserved, which both build paths keep (no FTZ flag: .amdhsa_float_denorm_mode_32 3); the
 // exact-zero golden sets would catch a flushing build.
 __device__ __forceinline__ uint32_t hd31(float x) { return fu(x - 1.40129846e-45f); }
-#elif PL_SC_LANE31
-__device__ __forceinline__ uint32_t hd31(float x) {
-    return (uint32_t)__builtin_elementwise_sub_sat((int32_t)fu(x), (int32_t)1);
-}
-#else
-__device__ __forceinline__ uint32_t hd31(float x) { return (x > 0.0f) ? 0u : 0x80000000u; }
-#endif
 __device__ __forceinline__ uint32_t hd(float x) { return (x > 0.0f) ? 0u : 1u; }
 
 // wave-wide "any lane": the ballot builtin directly (hiprtc's __any materialises the predicate
 // as 0/1 and compares it again: +400 VALU and +300 branches at (512,1024))
 __device__ __forceinline__ bool any_lane(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-__device__ __forceinline__ uint64_t ballot_lanes(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 struct Lane {
-#if PL_SC_LANE31
     // lo31[t]: 0x80000000 if this lane holds the low element of its pair at
     // level 2^t, else 0 (bitop3 operands; opaque to the compiler, see decode())
     uint32_t lo31[5];
     __device__ __forceinline__ uint32_t lom(int t) const { return (uint32_t)((int32_t)lo31[t] >> 31); }
-#else
-    uint32_t lom_[5];  // lom[t]: all-ones if this lane holds the low element at level 2^t
-    __device__ __forceinline__ uint32_t lom(int t) const { return lom_[t]; }
-#endif
     float lmax;
-    const float* chl;  // PL_SC_CH_LDS: this lane's first LDS channel word (slot NS/2), stride 64 words
+    const float* chl;  // Ch<C>::CHL: this lane's first LDS channel word (slot NS/2), stride 64 words
 };
 
 // ---------------- reductions over the G lanes of a codeword (all lanes get the result) ----
@@ -336,19 +276,6 @@ __device__ __forceinline__ float grp_sumf(float v) {
     if constexpr (LG >= 1) v = v + mirf<2>(v);
     return v;
 }
-// wave mask with the lowest lane of every aligned S-lane block set
-template <int S>
-__device__ __forceinline__ constexpr uint64_t blocklow() {
-    return S == 1 ? ~0ull : S == 2 ? 0x5555555555555555ull : S == 4 ? 0x1111111111111111ull
-         : S == 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
-}
-// True if some S-lane block whose lanes are set in `live` has two or more lanes set in `m`
-// (m must have at least one lane set in every block): subtracting 1 per block clears each
-// block's lowest set lane without borrowing across blocks.
-template <int S>
-__device__ __forceinline__ bool multi_in_block(uint64_t m, uint64_t live) {
-    return ((m & (m - blocklow<S>())) & live) != 0;
-}
 
 // ---------------- lane-level nodes: size 2^s <= G, one (replicated) LLR per lane ----------
 // Partial sums are returned as bit-31 flags (0 / 0x80000000) so g consumes them directly.
@@ -368,12 +295,6 @@ __device__ uint32_t lnode(float a, const Lane& ln);
 // 1 exp + 1 log per lane (S < G) or 2 + 1 (S = G) instead of 3 + 2.
 // Inlined, the lane-level f drops its call overhead (argument moves, the ABI's register
 // constraints); only with a fixed range (PL_EXF_RANGE != 0), where it has no full-range path.
-#ifndef PL_SC_FLANE_INLINE
-#define PL_SC_FLANE_INLINE 0
-#endif
-#if PL_SC_FLANE_INLINE && PL_EXF_RANGE == 0
-#error "PL_SC_FLANE_INLINE needs PL_EXF_RANGE 1 or 2"
-#endif
 #if PL_SC_FLANE_INLINE
 #define PL_FLANE_ATTR __attribute__((always_inline))
 #else
@@ -387,7 +308,6 @@ __device__ PL_FLANE_ATTR float f_lane_exact(float a, float y, uint32_t role31, f
     const bool A = (int32_t)role31 < 0;
     float arg;
     if constexpr (TOP) {
-#if PL_EXF_LEAN
         // e^(x+y) from the pair's two fp64 exps (exactf.h exp_sum) instead of a third exp
         const double ed = plx::exp_d(xc);
         const unsigned long long eb = (unsigned long long)__double_as_longlong(ed);
@@ -396,11 +316,6 @@ __device__ PL_FLANE_ATTR float f_lane_exact(float a, float y, uint32_t role31, f
         const float e = (float)ed;
         const float es = e + (float)edp;  // e^x + e^y in both lanes of the pair
         const float e1 = plx::exp_sum(ed, edp, xc, yc);
-#else
-        const float e = plx::exp_cr(xc);
-        const float es = e + mirf<S>(e);  // e^x + e^y in both lanes of the pair
-        const float e1 = plx::exp_cr(xc + yc);
-#endif
         arg = A ? 1.0f + e1 : es;
     } else {
         const float e = plx::exp_cr(A ? xc + yc : xc);
@@ -421,42 +336,24 @@ __device__ __forceinline__ uint32_t lsplit(float a, const Lane& ln) {
     uint32_t bl = 0;
     if constexpr (nt<C>(s - 1, P) != R0) {
         float x;
-        if constexpr (C::FM == 1 && PL_SC_FEX_LANE) {
+        if constexpr (C::FM == 1) {
             // role bit: the pair's low element (S = G), the low half of the 2S-block (S < G)
-#if PL_SC_LANE31
             const uint32_t role = s == C::LOG_G ? ln.lo31[s] : ln.lo31[s + 1];
-#else
-            const uint32_t role = s == C::LOG_G ? ln.lom(s) : ln.lom(s + 1);
-#endif
             x = f_lane_exact<S, s == C::LOG_G>(a, y, role, ln.lmax);
         } else {
             x = fop<C::FM, lchild<C>(s, P)>(a, y, ln.lmax);
         }
         bl = lnode<C, s - 1, P>(x, ln);
     }
-#if PL_SC_LANE31
     // both lanes of the pair evaluate (1-2u) alpha_lo + alpha_hi: the low lane flips its own
     // value (bitop3 S1 ^ (S0 & S2) with the lane's bit-31 mask), the high lane keeps its own, and
-    // one DPP add sums the pair in both lanes (fp32 addition is commutative: same bits)
-#if PL_SC_G_NODPP
-    // the same sum without reading the just-flipped value across lanes (no DPP hazard wait): the
-    // low lane flips its own value, the high lane the partner's copy y (taken before the left
-    // subtree), and both add -- the same two operands, so the same bits
-    const float x = uf(__builtin_amdgcn_bitop3_b32(bl, fu(a), ln.lo31[s], 0x6c)) +
-                    uf(__builtin_amdgcn_bitop3_b32(bl, fu(y), ln.lo31[s] ^ 0x80000000u, 0x6c));
-#else
+    // one DPP add sums the pair in both lanes (fp32 addition is commutative: same bits).  Two
+    // flips and a plain add -- the high lane flipping its copy y of the partner's value, no DPP
+    // read of a fresh value and no hazard s_nop -- was 1.3 % slower at (512,1024) (A/B r04zl).
     const float v = uf(__builtin_amdgcn_bitop3_b32(bl, fu(a), ln.lo31[s], 0x6c));
     const float x = v + mirf<S>(v);
-#endif
     const uint32_t br = lnode<C, s - 1, P + S / 2>(x, ln);
     return __builtin_amdgcn_bitop3_b32(bl, br, ln.lo31[s], 0x6c);  // br ^ (bl & lo31)
-#else
-    const uint32_t L = ln.lom(s);
-    const float x = uf(__builtin_amdgcn_bitop3_b32(bl, fu(a), L, 0x6c)) +
-                    uf(__builtin_amdgcn_bitop3_b32(bl, fu(y), L, 0x9c));
-    const uint32_t br = lnode<C, s - 1, P + S / 2>(x, ln);
-    return br ^ (bl & L);
-#endif
 }
 
 template <class C, int s, int P>
@@ -477,15 +374,10 @@ __device__ __forceinline__ uint32_t lnode(float a, const Lane& ln) {
         v = v + mirf<2>(v);
         return hd31(v);
     } else if constexpr (T == R1 && C::FM == 0) {
-#if PL_SC_LANE31
         if (!any_lane(a == 0.0f)) return fu(a);  // bit 31 = the decision
-#else
-        if (!any_lane(a == 0.0f)) return fu(a) & 0x80000000u;
-#endif
         return lsplit<C, s, P>(a, ln);
     } else if constexpr (T == SPC && C::FM == 0) {
         // magnitudes compared as integers (non-negative floats order like their bit patterns)
-        constexpr int S = 1 << s;
         const uint32_t b = fu(a) & 0x80000000u;
         const uint32_t ab = fu(a) & 0x7FFFFFFFu;
         uint32_t par = b, mn = ab;
@@ -495,17 +387,13 @@ __device__ __forceinline__ uint32_t lnode(float a, const Lane& ln) {
         par ^= mir<2>(par);
         mn = min(mn, mir<2>(mn));
         const bool eq = ab == mn;
-#if PL_SC_SPC_BALLOT
-        const bool bad_lane = (ab == 0u) | ((par != 0u) & (mn >= fu(ln.lmax)));
-        const bool bad = any_lane(bad_lane) || multi_in_block<S>(ballot_lanes(eq), ballot_lanes(par != 0u));
-#else
+        // unique minimum by a DPP count; a SALU test on ballots of eq was measured slower
         uint32_t cnt = eq ? 1u : 0u;
         if constexpr (s >= 4) cnt += mir<16>(cnt);
         if constexpr (s >= 3) cnt += mir<8>(cnt);
         if constexpr (s >= 2) cnt += mir<4>(cnt);
         cnt += mir<2>(cnt);
         const bool bad = any_lane((ab == 0u) | ((par != 0u) & ((cnt != 1u) | (mn >= fu(ln.lmax)))));
-#endif
         if (!bad) return b ^ (eq ? par : 0u);
         return lsplit<C, s, P>(a, ln);
     } else {
@@ -514,16 +402,18 @@ __device__ __forceinline__ uint32_t lnode(float a, const Lane& ln) {
 }
 
 // ---------------- in-lane nodes: size 2^s >= 2G, E = 2^s / G slots per lane ---------------
-// Partial sums of a node with E <= PL_SC_WIDE slots per lane are kept "wide": one word per slot
+// Partial sums of a node with E <= kWideSlots slots per lane are kept "wide": one word per slot
 // whose bit 31 is the bit (lower bits are don't-care), so g applies a flag with one bitop3 and the
 // combine [bl ^ br, br] is E/2 XORs -- no bit extraction (v_lshlrev) per g element.  Larger nodes
 // keep packed words (bit j = slot j), which bounds the registers of the long-lived upper stages.
+// 16 since the LDS channel half left VGPR headroom (profiles/r02t_sc_ab_dma_wide16.txt; 8 before).
+constexpr int kWideSlots = 16;
 template <int E>
 struct Wide {
     uint32_t w[E];
 };
 template <int E>
-using BV = typename Cond<(E <= PL_SC_WIDE), Wide<E>, Beta<E>>::type;
+using BV = typename Cond<(E <= kWideSlots), Wide<E>, Beta<E>>::type;
 
 template <int E>
 __device__ __forceinline__ uint32_t flag(const Wide<E>& b, int j) { return b.w[j]; }
@@ -533,7 +423,7 @@ __device__ __forceinline__ uint32_t flag(uint64_t b, int j) { return bit31(b, j)
 template <int E>
 __device__ __forceinline__ BV<E> bzero() {
     BV<E> r;
-    if constexpr (E <= PL_SC_WIDE) {
+    if constexpr (E <= kWideSlots) {
 #pragma unroll
         for (int j = 0; j < E; ++j) r.w[j] = 0u;
     } else {
@@ -568,7 +458,7 @@ __device__ __forceinline__ uint64_t packed(uint64_t b) { return b; }
 template <int H>
 __device__ __forceinline__ BV<2 * H> combine(const BV<H>& bl, const BV<H>& br) {
     BV<2 * H> r;
-    if constexpr (2 * H <= PL_SC_WIDE) {
+    if constexpr (2 * H <= kWideSlots) {
 #pragma unroll
         for (int j = 0; j < H; ++j) {
             r.w[j] = bl.w[j] ^ br.w[j];
@@ -588,11 +478,7 @@ __device__ BV<(1 << s) / C::G> node(const float (&a)[(1 << s) / C::G], const Lan
 template <class C, int s, int P>
 __device__ __forceinline__ BV<(1 << (s - 1)) / C::G> child(const float (&x)[(1 << (s - 1)) / C::G], const Lane& ln) {
     if constexpr ((1 << (s - 1)) == C::G) {
-#if PL_SC_WIDE >= 1
         return Wide<1>{{lnode<C, s - 1, P>(x[0], ln)}};
-#else
-        return (Beta<1>)(lnode<C, s - 1, P>(x[0], ln) >> 31);
-#endif
     } else {
         return node<C, s - 1, P>(x, ln);
     }
@@ -602,7 +488,7 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 // x[j] = g(a[j], a[j + H], flag j of bl) for j < H (polar_sc.py:49-53), two adds per v_pk_add_f32
 template <int H, typename B>
 __device__ __forceinline__ void gvec(const float (&a)[2 * H], const B& bl, float (&x)[H]) {
-    if constexpr (H >= 2 && PL_SC_PK_G) {
+    if constexpr (H >= 2) {
 #pragma unroll
         for (int j = 0; j < H; j += 2) {
             const f2v u = {flip31(a[j], flag(bl, j)), flip31(a[j + 1], flag(bl, j + 1))};
@@ -643,7 +529,7 @@ __device__ __forceinline__ Beta<E> signs(const float (&a)[E]) {
 }
 template <int E>
 __device__ __forceinline__ BV<E> from_packed(Beta<E> b) {
-    if constexpr (E <= PL_SC_WIDE) {
+    if constexpr (E <= kWideSlots) {
         Wide<E> r;
 #pragma unroll
         for (int j = 0; j < E; ++j) r.w[j] = bit31(b, j);
@@ -658,7 +544,7 @@ __device__ __forceinline__ BV<(1 << s) / C::G> node(const float (&a)[(1 << s) / 
     constexpr int E = (1 << s) / C::G;
     constexpr int T = nt<C>(s, P);
     using BT = Beta<E>;
-    constexpr bool WIDE = E <= PL_SC_WIDE;
+    constexpr bool WIDE = E <= kWideSlots;
 #if PL_SC_DIAG_SKIP_SPECIAL
     if constexpr (T == REP || T == SPC || T == R1) return from_packed<E>(signs<C, E>(a));  // diagnostic only
 #endif
@@ -711,16 +597,9 @@ __device__ __forceinline__ BV<(1 << s) / C::G> node(const float (&a)[(1 << s) / 
         BT eqm = 0;
 #pragma unroll
         for (int j = 0; j < E; ++j) eqm |= (BT)((fu(a[j]) & 0x7FFFFFFFu) == mn) << j;
-#if PL_SC_SPC_BALLOT
-        // unique minimum: no lane holds two, and no codeword group has two lanes holding one
-        const bool two = (eqm & (eqm - 1)) != 0;
-        const bool bad_lane = z | ((par != 0u) & (two | (mn >= fu(ln.lmax))));
-        const bool bad = any_lane(bad_lane) || multi_in_block<C::G>(ballot_lanes(eqm != 0), ballot_lanes(par != 0u));
-#else
         uint32_t cnt = (uint32_t)__popcll((unsigned long long)eqm);
         cnt = grp<C::LOG_G>(cnt, [](uint32_t u, uint32_t v) { return u + v; });
         const bool bad = any_lane(z | ((par != 0u) & ((cnt != 1u) | (mn >= fu(ln.lmax)))));
-#endif
         if (!bad) return from_packed<E>(par ? (BT)(b ^ eqm) : b);
         return split<C, s, P>(a, ln);
     } else {
@@ -753,7 +632,7 @@ __device__ __forceinline__ float valpha(const float (&ch)[C::NS], int side, uint
 template <class C, int SIDE>
 __device__ __forceinline__ void valphas(const float (&ch)[C::NS], uint64_t blr, float (&a)[C::NS / 2], float lmax) {
     constexpr int E = C::NS / 2;
-    if constexpr (SIDE == 0 && C::FM == 1 && E >= 2 && PL_SC_FEX_PAIR) {
+    if constexpr (SIDE == 0 && C::FM == 1 && E >= 2) {
         // exact f on the negated channel (vfroot), two elements per call
 #pragma unroll
         for (int j = 0; j < E; j += 2) {
@@ -776,15 +655,8 @@ __device__ __forceinline__ void valphas(const float (&ch)[C::NS], uint64_t blr, 
     }
 }
 
-struct NoHook {
-    __device__ __forceinline__ void operator()() const {}
-};
-
-// `after` runs once the channel registers are dead (their last read is done): the pipelined
-// decoder refills them with the next batch's channel there.
-template <class C, int SIDE, class Hook = NoHook>
-__device__ __forceinline__ Beta<C::NS / 2> half(float (&ch)[C::NS], uint64_t blr, const Lane& ln,
-                                                const Hook& after = Hook()) {
+template <class C, int SIDE>
+__device__ __forceinline__ Beta<C::NS / 2> half(float (&ch)[C::NS], uint64_t blr, const Lane& ln) {
     constexpr int s = C::LOG_N - 1, P = SIDE << s;
     constexpr int E = C::NS / 2;  // slots of the stage-(LOG_N-1) node per lane
     using BT = Beta<E>;
@@ -799,16 +671,13 @@ __device__ __forceinline__ Beta<C::NS / 2> half(float (&ch)[C::NS], uint64_t blr
         for (int j = C::NS / 2; j < C::NS; ++j) ch[j] = ln.chl[(j - C::NS / 2) * 64];
     }
     if constexpr (T == R0) {
-        after();
         return (BT)0;
     } else if constexpr (E == 1) {
         const float a = valpha<C>(ch, SIDE, blr, 0, ln.lmax);
-        after();
         return (BT)(lnode<C, s, P>(a, ln) >> 31);
     } else if constexpr (T != GEN) {
         float a[E];
         valphas<C, SIDE>(ch, blr, a, ln.lmax);
-        after();
         return packed(node<C, s, P>(a, ln));
     } else {
         constexpr int H = E / 2, h = 1 << (s - 1);
@@ -820,17 +689,10 @@ __device__ __forceinline__ Beta<C::NS / 2> half(float (&ch)[C::NS], uint64_t blr
         if constexpr (nt<C>(s - 1, P) != R0) {
             fvec<C::FM, SIDE == 0, H>(va, x, ln.lmax);
             bl = child<C, s, P>(x, ln);
-#if PL_SC_VA_RECOMPUTE
-            // recompute the virtual LLRs for the g pass instead of keeping them live across the
-            // left subtree (32 VGPRs at n = 1024): the opaque copy keeps the compiler from reusing
-            // the f-pass values
-#pragma unroll
-            for (int j = 0; j < C::NS; ++j) asm volatile("" : "+v"(ch[j]));
-            valphas<C, SIDE>(ch, blr, va, ln.lmax);
-#endif
         }
+        // va stays live across the left subtree (32 VGPRs at n = 1024): recomputing it for the g
+        // pass was -0.6 % at 3 waves per SIMD, +4.8 % at 4 (profiles/r02r_sc_ab_occupancy.txt)
         gvec<H>(va, bl, x);
-        after();
         const BH br = child<C, s, P + h>(x, ln);
         return packed(combine<H>(bl, br));
     }
@@ -906,7 +768,7 @@ template <class C>
 struct Emit {
     static constexpr int CW = 64 / C::G, WPL = (C::NS + 31) / 32, CWB = C::G * WPL * 4;
     static constexpr int KQ = C::K / 4, IT4 = (KQ + 63) / 64, IT1 = (C::K + 63) / 64;
-    static constexpr bool PRE = PL_SC_EMIT_PRE && (C::K & 3) == 0 && IT4 <= 2;  // table entries kept in VGPRs
+    static constexpr bool PRE = (C::K & 3) == 0 && IT4 <= 2;  // table entries preloaded at kernel start (8 VGPRs)
 };
 
 // bit (e & 31) of the u word at byte address wa + row_off
@@ -1189,18 +1051,18 @@ __device__ __forceinline__ void wave_lds_fence() {
 
 template <class C>
 __device__ __forceinline__ void load_channel(float (&chv)[C::NS], const float* __restrict__ llr, int64_t cw0,
-                                             int64_t bs, int lane, int res, float* chl_wave = nullptr) {
+                                             int64_t bs, int lane, int res, float* chl_wave) {
     const int64_t cw = cw0 + (lane >> C::LOG_G);
     const float* ch = llr + (size_t)(cw < bs ? cw : bs - 1) * C::N;
     if constexpr (Ch<C>::CHL) {
         // slots [0, NS/2) into VGPRs; slots [NS/2, NS) by LDS-DMA, one 256-byte LDS row per slot
         // (lane l's word at l * 4), so no VGPR holds them while the left half is decoded
 #pragma unroll
-        for (int j = 0; j < C::NS / 2; ++j) chv[j] = ld_ch(ch + j * C::G + res);
-#if PL_SC_DMA_ASM
+        for (int j = 0; j < C::NS / 2; ++j) chv[j] = ch[j * C::G + res];
         // saddr form: wave-uniform row base in an SGPR pair (slot offset j * 64 B as the 12-bit
         // immediate would also move the LDS address, so the base steps in SALU), this lane's
-        // 32-bit byte offset in a VGPR; M0 = the slot's LDS row.  No VALU per instruction.  The
+        // 32-bit byte offset in a VGPR; M0 = the slot's LDS row.  No VALU per instruction (the
+        // builtin form cost one 64-bit VALU address add each, profiles/r02t_sc_ab_dma_wide16.txt).  The
         // compiler does not track these loads: the reader waits with s_waitcnt vmcnt(0) (half()).
         // base row: the wave's lowest (clamped) row, so every lane's offset is >= 0 and < 16 KiB
         const int64_t row0 = cw0 < bs ? cw0 : bs - 1;
@@ -1213,49 +1075,20 @@ __device__ __forceinline__ void load_channel(float (&chv)[C::NS], const float* _
             const uint64_t sb = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a) |
                                 ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32);
             const uint32_t lb = (uint32_t)__builtin_amdgcn_readfirstlane((int)(lbase + (j - C::NS / 2) * 256));
-#if PL_SC_NT & 1
-            asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dword %0, %1 nt" ::"v"(voff), "s"(sb), "s"(lb) : "memory", "m0");
-#else
             asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(sb), "s"(lb) : "memory", "m0");
-#endif
         }
-#else
-#pragma unroll
-        for (int j = C::NS / 2; j < C::NS; ++j)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ch + j * C::G + res),
-                                             (__attribute__((address_space(3))) void*)(chl_wave + (j - C::NS / 2) * 64),
-                                             4, 0, (PL_SC_NT & 1) ? 2 : 0);
-#endif
     } else {
 #pragma unroll
-        for (int j = 0; j < C::NS; ++j) chv[j] = ld_ch(ch + j * C::G + res);
+        for (int j = 0; j < C::NS; ++j) chv[j] = ch[j * C::G + res];
     }
 }
 
-// Hook for half<1>: reload the channel registers with the next batch once they are dead.
 template <class C>
-struct Refill {
-    float (&chv)[C::NS];
-    const float* __restrict__ llr;
-    int64_t ncw0, bs;
-    int lane, res;
-    __device__ __forceinline__ void operator()() const {
-        // keep the scheduler from hoisting the refill above the last reads of the old values;
-        // unconditional (past the end every lane re-reads row bs-1, a cache hit) so the old
-        // values are dead here on every path
-        __builtin_amdgcn_sched_barrier(0);
-        load_channel<C>(chv, llr, ncw0, bs, lane, res);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-};
-
-template <class C, class Hook>
-__device__ __forceinline__ void root_virtual(float (&chv)[C::NS], const Lane& ln, uint64_t& lo, uint64_t& hi,
-                                             const Hook& after) {
+__device__ __forceinline__ void root_virtual(float (&chv)[C::NS], const Lane& ln, uint64_t& lo, uint64_t& hi) {
     constexpr int NS = C::NS;
     using BH = Beta<NS / 2>;
     const BH bl = half<C, 0>(chv, 0, ln);
-    const BH br = half<C, 1>(chv, (uint64_t)bl, ln, after);
+    const BH br = half<C, 1>(chv, (uint64_t)bl, ln);
     if constexpr (NS / 2 >= 64) {
         lo = (uint64_t)(bl ^ br);
         hi = (uint64_t)br;
@@ -1270,8 +1103,8 @@ __device__ __forceinline__ void decode(const float* __restrict__ llr, int64_t bs
                                        const int32_t* __restrict__ info_loc, int k, float lmax,
                                        uint32_t* __restrict__ ulds, const uint32_t* __restrict__ ref = nullptr,
                                        const SimArgs* sa = nullptr) {
-    static_assert(OUT < OUT_CNT || (!PL_SC_PERSIST && !PL_SC_STAMPS && (PL_SC_ROOT_MODE == 0 || OUT == OUT_CNT)),
-                  "OUT_CNT / OUT_SIM: plain decoder only (OUT_CNT also with the stage-(n/2) root of PL_SC_ROOT_MODE 1)");
+    static_assert(OUT < OUT_CNT || (!PL_SC_STAMPS && (PL_SC_ROOT_MODE == 0 || OUT == OUT_CNT)),
+                  "OUT_CNT / OUT_SIM: no clock stamps; OUT_SIM only with the virtual root (PL_SC_ROOT_MODE 0)");
     constexpr int N = C::N, G = C::G, LG = C::LOG_G, NS = C::NS, CW = 64 / G;
     constexpr int WPL = (NS + 31) / 32;
     // the wave index is wave-uniform: as an SGPR value all batch/row address math is scalar
@@ -1279,7 +1112,6 @@ __device__ __forceinline__ void decode(const float* __restrict__ llr, int64_t bs
     const int q = lane & (G - 1);
     Lane ln;
     int res;
-#if PL_SC_LANE31
     {
         uint32_t lom[5];
         lane_layout<LG>(q, res, lom);
@@ -1291,42 +1123,17 @@ __device__ __forceinline__ void decode(const float* __restrict__ llr, int64_t bs
             asm volatile("" : "+v"(ln.lo31[t]));
         }
     }
-#else
-    lane_layout<LG>(q, res, ln.lom_);
-    ln.lom_[0] = 0u;
-#endif
     ln.lmax = lmax;
     if constexpr (C::FM == 1) plx::load_tables(threadIdx.x, blockDim.x);  // the exact f's exp / log tables
-    // PL_SC_CH_LDS: each wave's LDS is its channel rows; its u words reuse their first 64 * WPL
+    // Ch<C>::CHL: each wave's LDS is its channel rows; its u words reuse their first 64 * WPL
     // words once the right half has read them (same wave, LDS in order)
     constexpr int WLDS = Ch<C>::CHL ? (NS / 2) * 64 : 64 * WPL;  // LDS words per wave
     uint32_t* ubase = ulds + wave * WLDS;
     uint32_t* mine = ubase + lane * WPL;
     float* chl_wave = reinterpret_cast<float*>(ulds + wave * WLDS);
     ln.chl = chl_wave + lane;
-    static_assert(!Ch<C>::CHL || (!PL_SC_PERSIST && PL_SC_ROOT_MODE == 0 && NS / 2 >= WPL), "PL_SC_CH_LDS: plain decoder only");
+    static_assert(!Ch<C>::CHL || (PL_SC_ROOT_MODE == 0 && NS / 2 >= WPL), "Ch<C>::CHL: the virtual root only");
 
-#if PL_SC_PERSIST
-    // Persistent, software-pipelined: each wave walks batches of CW codewords with a stride of
-    // the whole grid; the next batch's channel is loaded into the channel registers as soon as
-    // their last read is done (3/4 through the tree), so its HBM latency overlaps the rest of
-    // the tree and the output of this batch instead of stalling every wave at the same instant.
-    const int64_t stride = (int64_t)gridDim.x * kWaves * CW;
-    int64_t cw0 = ((int64_t)blockIdx.x * kWaves + wave) * CW;
-    int4 il[2];
-    preload_info<C>(info_loc, il, lane);
-    float chv[NS];
-    load_channel<C>(chv, llr, cw0, bs, lane, res);
-    for (; cw0 < bs; cw0 += stride) {
-        const int64_t ncw0 = cw0 + stride;
-        uint64_t lo, hi;
-        root_virtual<C>(chv, ln, lo, hi, Refill<C>{chv, llr, ncw0, bs, lane, res});
-        to_u<C>(lo, hi, ln, mine);
-        wave_lds_fence();
-        emit<C, OUT>(ubase, cw0, bs, out, info_loc, il, lane);
-        wave_lds_fence();
-    }
-#else
     const int64_t cw0 = ((int64_t)blockIdx.x * kWaves + wave) * CW;
 #if PL_SC_STAMPS
     // diagnostic build: per-wave clock stamps into the output's tail (tools/static_probe.py)
@@ -1361,7 +1168,7 @@ __device__ __forceinline__ void decode(const float* __restrict__ llr, int64_t bs
         hi = acc >> 1;
     }
 #else
-    root_virtual<C>(chv, ln, lo, hi, NoHook());
+    root_virtual<C>(chv, ln, lo, hi);
 #endif
     if constexpr (OUT == OUT_SIM) {
         sim_count<C>(lo, hi, ln, gsim, cw0, bs, lane, static_cast<int32_t*>(out), blockIdx.x * kWaves + wave);
@@ -1436,132 +1243,11 @@ __device__ __forceinline__ void decode(const float* __restrict__ llr, int64_t bs
         d[7] = rt;
     }
 #endif
-#endif
 }
-
-
-#if PL_SC_PERSIST == 2
-// LDS layout of the staged kernel (one __shared__ array: a second LDS object can make the
-// compiler drain the copies early): [kWaves][64 lanes][WPL] u words, then per wave CW channel
-// rows of N floats + a 16-float pad (rows r and r + 1 start in opposite halves of the 32 banks,
-// so the ds_read_b32 of the residue layout is conflict-free).
-template <class C>
-struct Staged {
-    static constexpr int CW = 64 / C::G, WPL = (C::NS + 31) / 32, ROW = C::N + 16;
-    static constexpr int U_WORDS = kWaves * 64 * WPL;
-    static constexpr int WORDS = U_WORDS + kWaves * CW * ROW;
-    static constexpr int COPIES = CW * (C::N / 256);  // 1-KiB copies per batch
-    static constexpr int KQ = C::K / 4;               // float4 output chunks per row
-    static constexpr int IT4 = (KQ + 63) / 64, IT1 = (C::K + 63) / 64;
-    // store instructions one batch's emit issues after the next batch's copies (full batches):
-    // the counted wait before reading the staging buffer leaves exactly these outstanding
-    static constexpr int ST_VEC = IT4 * CW, ST_SCALAR = IT1 * CW;
-};
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0, "");
-    if constexpr (N >= 63) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Rows cw0 .. cw0+CW-1 (clamped to bs-1) into the wave's staging rows, 1 KiB per instruction.
-template <class C>
-__device__ __forceinline__ void stage_copy(const float* __restrict__ llr, int64_t cw0, int64_t bs, float* rows,
-                                           int lane) {
-    using S = Staged<C>;
-#pragma unroll
-    for (int r = 0; r < S::CW; ++r) {
-        const int64_t cw = cw0 + r < bs ? cw0 + r : bs - 1;
-        const float* src = llr + (size_t)cw * C::N + lane * 4;
-#pragma unroll
-        for (int i = 0; i < C::N / 256; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 256),
-                                             (__attribute__((address_space(3))) void*)(rows + r * S::ROW + i * 256),
-                                             16, 0, 0);
-    }
-}
-
-template <class C, int OUT>
-__device__ __forceinline__ void decode_staged(const float* __restrict__ llr, int64_t bs, void* __restrict__ out,
-                                              const int32_t* __restrict__ info_loc, int k, float lmax,
-                                              uint32_t* __restrict__ lds) {
-    using S = Staged<C>;
-    constexpr int G = C::G, LG = C::LOG_G, NS = C::NS, CW = S::CW, WPL = S::WPL;
-    static_assert(C::N >= 256 && C::N % 256 == 0, "staged channel rows are whole 1-KiB copies");
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int q = lane & (G - 1);
-    Lane ln;
-    int res;
-#if PL_SC_LANE31
-    {
-        uint32_t lom[5];
-        lane_layout<LG>(q, res, lom);
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-            ln.lo31[t] = t ? lom[t] & 0x80000000u : 0u;
-            asm volatile("" : "+v"(ln.lo31[t]));
-        }
-    }
-#else
-    lane_layout<LG>(q, res, ln.lom_);
-    ln.lom_[0] = 0u;
-#endif
-    ln.lmax = lmax;
-    // exact f would add the tables' LDS object next to the single Staged array (see above: the
-    // compiler may then drain the copies early); the staged kernel is a rejected min-sum A/B
-    static_assert(C::FM == 0, "PL_SC_PERSIST == 2 (staged kernel): min-sum codes only");
-    uint32_t* ubase = lds + wave * 64 * WPL;
-    uint32_t* mine = lds + (wave * 64 + lane) * WPL;
-    float* rows = reinterpret_cast<float*>(lds + S::U_WORDS) + wave * CW * S::ROW;
-    const float* myrow = rows + (lane >> LG) * S::ROW + res;
-    const bool vec = OUT == OUT_F32 && (C::K & 3) == 0 && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-
-    const int64_t stride = (int64_t)gridDim.x * kWaves * CW;
-    int64_t cw0 = ((int64_t)blockIdx.x * kWaves + wave) * CW;
-    if (cw0 >= bs) return;  // wave-uniform; no block-wide barrier below
-    int4 il[2];
-    preload_info<C>(info_loc, il, lane);
-    stage_copy<C>(llr, cw0, bs, rows, lane);
-    wait_vm<0>();
-    for (;;) {
-        float chv[NS];
-#pragma unroll
-        for (int j = 0; j < NS; ++j) chv[j] = myrow[j * G];
-        // the reads must have returned before the next copy overwrites the rows
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const int64_t ncw0 = cw0 + stride;
-        const bool more = ncw0 < bs;
-        if (more) stage_copy<C>(llr, ncw0, bs, rows, lane);
-        uint64_t lo = 0, hi = 0;
-        root_virtual<C>(chv, ln, lo, hi, NoHook());
-        to_u<C>(lo, hi, ln, mine);
-        wave_lds_fence();
-        emit<C, OUT>(ubase, cw0, bs, out, info_loc, il, lane);
-        wave_lds_fence();
-        if (!more) break;
-        // this batch was full (a partial batch is the last one): its emit issued exactly
-        // ST_VEC / ST_SCALAR stores after the copies
-        if (vec) wait_vm<S::ST_VEC>();
-        else wait_vm<S::ST_SCALAR>();
-        cw0 = ncw0;
-    }
-    (void)k;
-}
-#endif
 
 }  // namespace pls
 
 // Entry points instantiated per code: the including translation unit defines PlCode first.
-#if PL_SC_PERSIST == 2
-#define PL_SC_ENTRY(CODE, NAME, OUTK)                                                                        \
-    extern "C" __global__ __launch_bounds__(64 * pls::kWaves, 2) void NAME(                                  \
-        const float* __restrict__ llr, int64_t bs, void* __restrict__ out, const int32_t* __restrict__ info_loc, \
-        int k, float lmax) {                                                                                  \
-        __shared__ uint32_t lds[pls::Staged<CODE>::WORDS];                                                   \
-        pls::decode_staged<CODE, OUTK>(llr, bs, out, info_loc, k, lmax, lds);                                \
-    }
-#else
 #define PL_SC_ENTRY(CODE, NAME, OUTK)                                                                        \
     extern "C" __global__ __launch_bounds__(64 * pls::kWaves, PL_SC_MINW) void NAME(                         \
         const float* __restrict__ llr, int64_t bs, void* __restrict__ out, const int32_t* __restrict__ info_loc, \
@@ -1570,12 +1256,8 @@ __device__ __forceinline__ void decode_staged(const float* __restrict__ llr, int
                                                     : pls::kWaves * 64 * ((CODE::NS + 31) / 32)];              \
         pls::decode<CODE, OUTK>(llr, bs, out, info_loc, k, lmax, ulds);                                      \
     }
-#endif
-#ifndef PL_SC_PERSIST_BPC
-#define PL_SC_PERSIST_BPC 2  // resident blocks per CU the launcher gives a persistent kernel
-#endif
-// decode + error count against packed reference bits (pl_sc_decode_count); plain decoder only
-#if PL_SC_PERSIST || PL_SC_STAMPS
+// decode + error count against packed reference bits (pl_sc_decode_count); not in a stamps build
+#if PL_SC_STAMPS
 #define PL_SC_CNT_ENTRY(CODE)
 #else
 #define PL_SC_CNT_ENTRY(CODE)                                                                                \
@@ -1589,10 +1271,7 @@ __device__ __forceinline__ void decode_staged(const float* __restrict__ llr, int
 #endif
 // producer + decode + error count (pl_sc_sim_count); codes with 64 slots per lane (jit.cpp
 // defines PL_SC_SIM for those and emits the code's INFO_LANE table)
-#ifndef PL_SC_SIM
-#define PL_SC_SIM 0
-#endif
-#if !PL_SC_SIM || PL_SC_PERSIST || PL_SC_STAMPS || PL_SC_ROOT_MODE
+#if !PL_SC_SIM || PL_SC_STAMPS || PL_SC_ROOT_MODE
 #define PL_SC_SIM_ENTRY(CODE)
 #else
 #define PL_SC_SIM_ENTRY(CODE)                                                                                \
@@ -1607,8 +1286,6 @@ __device__ __forceinline__ void decode_staged(const float* __restrict__ llr, int
     }
 #endif
 #define PL_SC_STATIC_KERNELS(CODE)                                                                           \
-    extern "C" __device__ const int pl_sc_persistent = PL_SC_PERSIST;                                       \
-    extern "C" __device__ const int pl_sc_blocks_per_cu = PL_SC_PERSIST_BPC;                                \
     extern "C" __device__ const int pl_sc_waves = PL_SC_KWAVES;                                            \
     PL_SC_ENTRY(CODE, pl_sc_static_f32, pls::OUT_F32)                                                        \
     PL_SC_ENTRY(CODE, pl_sc_static_u8, pls::OUT_U8)                                                          \

@@ -289,7 +289,8 @@ def test_diagnostic_macros_refuse_release_builds(tmp_path):
     import subprocess
     from polar_amd import build as b
     hipcc = b._hipcc()
-    for src, macro in (("sc_static.h", "PL_SC_DIAG_NO_TREE"), ("scl_tree_kernel.hip", "PL_SCL_DIAG_SKIP_V"),
+    for src, macro in (("sc_static.h", "PL_SC_DIAG_NO_TREE"), ("sc_static.h", "PL_SC_STAMPS"),
+                       ("scl_tree_kernel.hip", "PL_SCL_DIAG_SKIP_V"),
                        ("sc_kernel.hip", "PL_SC_DIAG_NOSTORE"), ("channel_kernel.hip", "PL_AWGN_DIAG")):
         r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-x", "hip",
                             f"-D{macro}=1", f"-I{b.OBJ}", os.path.join(b.CSRC, src)],
@@ -323,6 +324,49 @@ def test_scl_development_macros_compile():
         return macro, r.returncode, r.stderr[-600:]
     with ThreadPoolExecutor(8) as ex:
         bad = [(m, e) for m, rc, e in ex.map(one, macros) if rc]
+    assert not bad, bad[:2]
+
+
+def test_sc_development_macros_compile(tmp_path):
+    """The development-only paths of the specialised SC kernel -- every PL_SC_DIAG_* ablation and
+    the clock stamps PL_SC_STAMPS = 1 -- still compile for gfx950, for a small min-sum code and the
+    (512,1024) one (no build compiles them otherwise: tools/sc_ab.py, tools/sc_variants.py and
+    tools/static_probe.py pass these macros by hand).  Every macro the header reads has its default
+    in the one block at its top, and none of the development ones reaches a release build."""
+    import re
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    import polar_amd
+    from polar_amd import _lib, build as b
+    hipcc = b._hipcc()
+    src = open(os.path.join(b.CSRC, "sc_static.h")).read()
+    begin, end = src.index("// ---- Build parameters"), src.index("// ---- end of the build parameters")
+    block = src[begin:end]
+    diag = sorted(set(re.findall(r"\bPL_SC_DIAG_[A-Z0-9_]+\b", src)))
+    defaults = set(re.findall(r"^#ifndef (PL_SC_DIAG_[A-Z0-9_]+)\n#define \1 0\b", block, re.M))
+    assert set(diag) == defaults, set(diag) ^ defaults  # every ablation has its default in the block at the top
+    assert {"PL_SC_DIAG_SKIP_LANE", "PL_SC_DIAG_NO_LOAD", "PL_SC_DIAG_NO_TREE", "PL_SC_DIAG_SKIP_SPECIAL"} <= defaults
+    assert re.search(r"^#ifndef PL_SC_STAMPS\n#define PL_SC_STAMPS 0\b", block, re.M)
+    guard = re.search(r"#if !defined\(PL_DEV\) && \((.*?)\)\n#error", block, re.S).group(1)
+    assert set(re.findall(r"PL_SC_[A-Z0-9_]+", guard)) == defaults | {"PL_SC_STAMPS"}  # none reaches a release build
+    assert not re.findall(r"^#ifndef PL_SC_(?!STATIC_H\b)\w+", src[:begin] + src[end:], re.M)  # no default elsewhere
+    macros = [f"{m}=1" for m in diag] + ["PL_SC_STAMPS=1"]
+    small = np.zeros(64, np.uint8)
+    small[:32] = 1
+    big = polar_amd.frozen_mask(polar_amd.reference_frozen_pos(512, 1024).numpy(), 1024)
+    jobs = []
+    for tag, m in (("n64", small), ("n1024", big)):
+        path = str(tmp_path / f"sc_{tag}.hip")
+        open(path, "w").write("#define PL_DEV 1\n" + _lib.sc_source(len(m), m, 0)[0])
+        jobs += [(path, macro) for macro in macros]
+
+    def one(job):
+        path, macro = job
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only",
+                            f"-D{macro}", path], capture_output=True, text=True, timeout=600)
+        return (os.path.basename(path), macro), r.returncode, r.stderr[-600:]
+    with ThreadPoolExecutor(8) as ex:
+        bad = [(j, e) for j, rc, e in ex.map(one, jobs) if rc]
     assert not bad, bad[:2]
 
 

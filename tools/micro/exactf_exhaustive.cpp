@@ -1,5 +1,5 @@
 // Development aid (host): EXHAUSTIVE correct-rounding check of the SC exact f's exp and log forms
-// (csrc/exactf.h exp_d / log_d, PL_EXF_LEAN, mirrored op for op in exactf_rounding.cpp) over every
+// (csrc/exactf.h exp_d / log_d, the lean forms, mirrored op for op in exactf_rounding.cpp) over every
 // fp32 argument they can receive: exp on every fp32 x with |x| <= 87 (the f forms |x| <= 86 at
 // llr_max <= 43), log on every positive normal fp32.  The reference value is expl / logl (x87
 // extended, ~2^-63 relative) rounded to fp32; an argument whose extended value lies within 2^-58 of

@@ -1,5 +1,5 @@
 // Development aid (host): correct rounding of the table-driven exp_cr / log_cr of csrc/exactf.h
-// (PL_EXF_LEAN forms, and the f with e^(x+y) from the product e^x e^y e^d)
+// (the lean forms, and the f with e^(x+y) from the product e^x e^y e^d)
 // (the same tables, tools/micro/exactf_tables.inc, and the same operation sequence in fp64 with
 // fma), against expl / logl rounded to fp32 -- 5e7 arguments per range -- and the exact f built
 // from them against f with every transcendental correctly rounded.
@@ -12,7 +12,7 @@
 
 #include "exactf_tables.inc"
 
-static double exp_d(float xf) {  // exactf.h exp_d (PL_EXF_LEAN: 2^(j/256) one-part, degree 4)
+static double exp_d(float xf) {  // exactf.h exp_d (lean: 2^(j/256) one-part, degree 4)
     const double x = xf;
     const double t = fma(x, kTabInvC1, 0x1.8p52);
     uint64_t tb;
@@ -48,7 +48,7 @@ static double log_d(float xf) {  // exactf.h log_d
     const double l1 = fma(r2, p, r);
     const double de = e;
     const double hi = fma(de, kTabLn2Hi, kTabLogL[2 * j]);
-    const double lo = fma(de, kTabLn2Lo, l1);  // PL_EXF_LEAN: no low part of -ln c_j
+    const double lo = fma(de, kTabLn2Lo, l1);  // lean: no low part of -ln c_j
     return hi + lo;
 }
 static float exp_cr(float x) { return (float)exp_d(x); }
@@ -57,7 +57,7 @@ static float exp_ref(float x) { return (float)expl((long double)x); }
 static float log_ref(float x) { return (float)logl((long double)x); }
 
 // exactf.h exp_sum: fp32 e^(fl(xc + yc)) from the fp64 e^xc, e^yc and the Fast2Sum error d
-static float exp_sum(double ex, double ey, float xc, float yc) {  // PL_EXF_TWOSUM: the exact error by TwoSum
+static float exp_sum(double ex, double ey, float xc, float yc) {  // the exact error by TwoSum
     volatile float s = xc + yc;
     volatile float bb = s - xc;
     volatile float t = s - bb;
@@ -67,7 +67,7 @@ static float exp_sum(double ex, double ey, float xc, float yc) {  // PL_EXF_TWOS
     const double d = -(double)e;
     return (float)(ex * ey * fma(d, fma(d, 0.5, 1.0), 1.0));
 }
-// exactf.h f_exact (PL_EXF_LEAN)
+// exactf.h f_exact (the lean form)
 static float f_lean(float x, float y, float lmax) {
     const float xc = fminf(fmaxf(x, -lmax), lmax), yc = fminf(fmaxf(y, -lmax), lmax);
     const double ex = exp_d(xc), ey = exp_d(yc);

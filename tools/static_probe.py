@@ -63,7 +63,7 @@ def info_loc(mask, name=None):
 def code_src(mask, fm=0, name=None):
     n = len(mask); logn = n.bit_length() - 1; lg = lg_of(n, name)
     nt = ntable(mask)
-    return (f"struct PlCode {{ static constexpr int N = {n}, LOG_N = {logn}, LOG_G = {lg}, G = {1<<lg}, NS = {n>>lg}, FM = {fm};\n"
+    return (f"struct PlCode {{ static constexpr int N = {n}, K = {int((mask == 0).sum())}, LOG_N = {logn}, LOG_G = {lg}, G = {1<<lg}, NS = {n>>lg}, FM = {fm};\n"
             f"  static constexpr unsigned char NT[{2*n}] = {{{','.join(map(str, nt))}}}; }};\n")
 
 import numpy as np
@@ -75,10 +75,9 @@ def build(k, n, name, flags):
     os.makedirs(OUT, exist_ok=True)
     src = os.path.join(OUT, f"st_{name}.hip")
     open(src, "w").write('#include "sc_static.h"\n' + code_src(mask, int(os.environ.get("PROBE_FM", "0")), name) + "PL_SC_STATIC_KERNELS(PlCode)\n" + r'''
-extern "C" int st_launch(const float* llr, long bs, void* out, const int* info_loc, int k, float lmax, void* st, long pf) {
+extern "C" int st_launch(const float* llr, long bs, void* out, const int* info_loc, int k, float lmax, void* st) {
     const long per = (long)pls::kWaves * (64 / PlCode::G);
-    long blocks = (bs + per - 1) / per;
-    if (pf > 0 && pf < blocks) blocks = pf;  // persistent variants: pf = grid size in blocks
+    const long blocks = (bs + per - 1) / per;
     hipLaunchKernelGGL(pl_sc_static_f32, dim3((unsigned)blocks), dim3(64 * pls::kWaves), 0,
                        (hipStream_t)st, llr, (int64_t)bs, out, info_loc, k, lmax);
     return (int)hipGetLastError();
@@ -86,7 +85,7 @@ extern "C" int st_launch(const float* llr, long bs, void* out, const int* info_l
 ''')
     so = os.path.join(OUT, f"st_{name}.so")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                           "-ffp-contract=off", f"-I{CSRC}", *flags, src, "-o", so])
+                           "-ffp-contract=off", "-DPL_DEV=1", f"-I{CSRC}", *flags, src, "-o", so])
     print("built", so)
 
 def run(k, n, names):
@@ -119,13 +118,12 @@ def run(k, n, names):
     for name in names:
         iloc = torch.from_numpy(info_loc(mask, name)).to(dev)
         L = ctypes.CDLL(os.path.join(OUT, f"st_{name}.so"))
-        L.st_launch.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_long]
-        pfs = [int(v) for v in os.environ.get("PROBE_PF", "0").split(",")]
+        L.st_launch.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]
         if "stamp" in name:
             nw = (bs // (64 // (1 << lg_of(n))))
             big = torch.zeros(bs * k + nw * 16 + 64, device=dev)
-            L.st_launch(llr.data_ptr(), bs, big.data_ptr(), iloc.data_ptr(), k, 30.0, st, 0)
-            L.st_launch(llr.data_ptr(), bs, big.data_ptr(), iloc.data_ptr(), k, 30.0, st, 0)
+            L.st_launch(llr.data_ptr(), bs, big.data_ptr(), iloc.data_ptr(), k, 30.0, st)
+            L.st_launch(llr.data_ptr(), bs, big.data_ptr(), iloc.data_ptr(), k, 30.0, st)
             torch.cuda.synchronize()
             d = big[bs * k: bs * k + nw * 16].view(torch.int64).view(nw, 8).cpu().numpy()
             t0 = d[:, 0].min()
@@ -143,14 +141,13 @@ def run(k, n, names):
         for x in (llr, x2, x3):
             want = ops.sc_decode(plan, x)
             out.fill_(7)
-            assert L.st_launch(x.data_ptr(), bs, out.data_ptr(), iloc.data_ptr(), k, 30.0, st, pfs[-1]) == 0
+            assert L.st_launch(x.data_ptr(), bs, out.data_ptr(), iloc.data_ptr(), k, 30.0, st) == 0
             torch.cuda.synchronize()
             nbad = int((out != want).any(dim=1).sum())
             ok &= nbad == 0
             if nbad: print(f"  {name}: {nbad} mismatching rows", flush=True)
-        for pf in pfs:
-            t = tm(lambda: L.st_launch(llr.data_ptr(), bs, out.data_ptr(), iloc.data_ptr(), k, 30.0, st, pf))
-            print(f"static[{name}] pf={pf} ({k},{n}): {t:.4f} ms  {bs / t / 1e3:.1f} Mcw/s  exact={ok}", flush=True)
+        t = tm(lambda: L.st_launch(llr.data_ptr(), bs, out.data_ptr(), iloc.data_ptr(), k, 30.0, st))
+        print(f"static[{name}] ({k},{n}): {t:.4f} ms  {bs / t / 1e3:.1f} Mcw/s  exact={ok}", flush=True)
 
     t_ref = tm(lambda: ops.sc_decode(plan, llr, out=ref_out))
     print(f"library kernel again ({k},{n}) bs={bs}: {t_ref:.4f} ms  {bs / t_ref / 1e3:.1f} Mcw/s", flush=True)
