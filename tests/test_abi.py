@@ -127,6 +127,14 @@ def test_list_plan_rejects_llr_max_above_700():
     mask = np.zeros(8, dtype=np.uint8)
     assert L.pl_plan_create(ctypes.byref(h), 8, mask.ctypes.data_as(ctypes.c_void_p), 4, 0, 701.0, 0) == _lib.PL_EINVAL
     assert b"700" in L.pl_last_error_string()
+    # 700.0 itself is inside the envelope: it passes the validation (and creates, given a device)
+    import torch
+    rc = L.pl_plan_create(ctypes.byref(h), 8, mask.ctypes.data_as(ctypes.c_void_p), 4, 0, 700.0, 0)
+    if torch.cuda.is_available():
+        assert rc == _lib.PL_OK, L.pl_last_error_string()
+        L.pl_plan_destroy(h)
+    else:
+        assert rc != _lib.PL_EINVAL and b"700" not in L.pl_last_error_string()
 
 
 def test_sc_source_and_cache_name():

@@ -15,8 +15,9 @@ evaluation may round the other way (none at all in the inputs as generated).
   * n = 8 ... 1024 with position 1 the only information bit: the in-lane f loops (f_exact2), the
     cross-lane stages and the n = 1024 channel half, llr_max 30 and 60;
   * the (128, 256) and (512, 1024) reference codes on AWGN logits at 1-3 dB.
-Both SC kernels, the specialised ones pre-built (polar_amd.build.reference_codes()).  Not pinned
-here: the list decoders' f (csrc/softplus.h), which makes no correct-rounding claim.
+Both SC kernels, the specialised ones pre-built (polar_amd.build.reference_codes()).  The list
+decoders' f and penalty (csrc/softplus.h), which make no correct-rounding claim, are pinned to a few
+ulp by tests/test_pm_ulp_gpu.py; NaN / Inf inputs remain unpinned everywhere.
 """
 import os
 import sys
