@@ -35,6 +35,8 @@
  *   pl_rate_recover  Polar5GDecoder.forward rate recovery my_sn/fec/polar/dec.py:621-654
  *   pl_osd_plan_create OSDecoder.__init__ my_sn/fec/osd/dec.py:22-53
  *   pl_osd_decode    OSDecoder.forward  my_sn/fec/osd/dec.py:148-192 (_find_mrb :107-147, _find_min_dist :82-106)
+ *   pl_bp_decode     the "iterative BP decoding" of my_sn/fec/polar/dec.py:1 and Polar5GDecoder's
+ *                    dec_type "BP" (named there, not implemented)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -361,6 +363,44 @@ int pl_osd_decode(const pl_osd_plan* plan, const float* llr_logits, int64_t bs, 
  * the stream's device is the caller's business, as for pl_crc_attach.  No allocation per call. */
 int pl_genie_count(int32_t n, int32_t f_mode, float llr_max, const float* llr_logits, const uint32_t* u_bits,
                    int64_t bs, int64_t* counts, float* leaf_out, void* hip_stream);
+
+/* Iterative belief-propagation (BP) decoding with soft output (polar_amd.BP_Dec; csrc/bp_kernel.hip): the
+ * "BP" decoder my_sn/fec/polar/dec.py names (its first line, and dec_type of Polar5GDecoder) and does not
+ * contain.  The only decoder here that returns soft information.
+ * plan: a list-size-1 plan; its n (2 <= n <= 1024), frozen set, f_mode and llr_max (lmax below) are used.
+ * llr_logits [bs, n] fp32 logits log P(1)/P(0); inside, an LLR is a = -logit (positive favours 0).
+ * Messages L[s][i] (towards u) and R[s][i] (towards the channel), s = 0 .. S = log2 n, on the encoder
+ * butterfly: for s = 1 .. S, h = 2^(s-1), every p whose index bit s-1 is 0, one unit joins (s-1, p),
+ * (s-1, p+h), (s, p), (s, p+h).  L[S][i] = clip(-logit[i]); R[0][i] = +lmax at frozen positions, 0 at
+ * information positions; every other message starts at 0.  clip(v) = med3(v, -lmax, lmax).
+ * f: PL_F_MINSUM: magnitude min(|x|, |y|, lmax) -- times scale, rounded to fp32 once, when scale < 1 --
+ * with the xor of the two sign bits; PL_F_EXACT: pl_sc_decode's exact f (inputs clipped inside, the
+ * full-range form when lmax > 43).
+ * One iteration: the R pass, s = 1 .. S, every unit:
+ *     R[s][p]   = clip(f(R[s-1][p], L[s][p+h] + R[s-1][p+h]))
+ *     R[s][p+h] = clip(f(R[s-1][p], L[s][p]) + R[s-1][p+h])
+ * then the L pass, s = S .. 1, every unit:
+ *     L[s-1][p]   = clip(f(L[s][p], L[s][p+h] + R[s-1][p+h]))
+ *     L[s-1][p+h] = clip(f(L[s][p], R[s-1][p]) + L[s][p+h])
+ * every + one fp32 rounding, the inner sum not clipped before f.  A stage writes each message once and
+ * reads only the neighbouring stage: the result does not depend on the schedule.
+ * Outputs after the last iteration run (any may be NULL, not all):
+ *   out_bits [bs, k], PL_OUT_F32 / PL_OUT_U8: !(L[0][i] > 0) at the information positions, ascending;
+ *   soft_u [bs, k] fp32: -L[0][i] there, logits log P(1)/P(0) like the input;
+ *   ext_x [bs, n] fp32: -R[S][i], the extrinsic logits of the code bits;
+ *   iters [bs] int32: the iterations the row ran.
+ * flags: 0 or PL_BP_EARLY_STOP: after each iteration, u^ = the hard decisions over all n positions (frozen
+ * ones 0) and x^[i] = !(L[S][i] + R[S][i] > 0); a row whose u^ encodes to x^ stops and keeps the messages
+ * of that iteration.  Without the flag, and for a row that never stops, iters is num_iter.
+ * No allocation and no host synchronisation: the call can be captured into a HIP graph.  bs == 0 is PL_OK.
+ * PL_EINVAL (the message names the argument): num_iter < 1, scale outside (0, 1], scale != 1 with
+ * PL_F_EXACT, a list plan, all four outputs NULL, negative bs, a stream of another device.  PL_ENOTSUP:
+ * n = 2048 (the messages of a codeword, (2 S + 1) n fp32, must fit one CU's LDS).  NaN and Inf inputs are
+ * not supported. */
+#define PL_BP_EARLY_STOP 1u
+int pl_bp_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, int32_t num_iter, float scale,
+                 uint32_t flags, void* out_bits, int32_t out_kind, float* soft_u, float* ext_x, int32_t* iters,
+                 void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

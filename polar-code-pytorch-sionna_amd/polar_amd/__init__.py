@@ -11,7 +11,8 @@ from .crc import CRCDecoder, CRCEncoder, int_mod_2  # noqa: F401
 from .frozen import F2, get_Kern_frozen_bits, reference_frozen_pos, frozen_mask  # noqa: F401
 from .osd import OSDecoder  # noqa: F401
 from .design import bit_channel_errors, select_frozen, design_frozen_pos  # noqa: F401
+from .bp import BP_Dec  # noqa: F401
 
-__all__ = ["SC_Dec", "SCL_Dec", "F2", "get_Kern_frozen_bits", "reference_frozen_pos", "frozen_mask", "ops",
+__all__ = ["SC_Dec", "SCL_Dec", "BP_Dec", "F2", "get_Kern_frozen_bits", "reference_frozen_pos", "frozen_mask", "ops",
            "CRCEncoder", "CRCDecoder", "int_mod_2", "OSDecoder", "bit_channel_errors", "select_frozen",
            "design_frozen_pos"]

@@ -20,6 +20,7 @@ PL_F_WIDE_RANGE = 0x100  # sc_source / pl_sc_specialize: the exact-f code object
 PL_OUT_F32, PL_OUT_U8 = 0, 1
 PL_PLAN_GENERIC, PL_PLAN_CACHE_ONLY, PL_PLAN_FAST_SCL, PL_PLAN_JIT = 1, 2, 4, 8
 PL_KERNEL_GENERIC, PL_KERNEL_SPECIALIZED, PL_KERNEL_SCL_SUBTREE = 0, 1, 2
+PL_BP_EARLY_STOP = 1
 
 _lock = threading.Lock()
 _lib = None
@@ -77,6 +78,7 @@ def _declare(L):
     L.pl_osd_plan_info.argtypes = [P, P, P, P, P]
     L.pl_osd_decode.argtypes = [P, P, i64, P, i32, P, P, P]
     L.pl_genie_count.argtypes = [i32, i32, ctypes.c_float, P, P, i64, P, P, P]
+    L.pl_bp_decode.argtypes = [P, P, i64, i32, ctypes.c_float, u32, P, i32, P, P, P, P]
     L.pl_last_error_string.restype = ctypes.c_char_p
     L.pl_version.restype = ctypes.c_char_p
     for f in (L.pl_plan_create, L.pl_plan_destroy, L.pl_plan_info, L.pl_plan_device, L.pl_sc_decode, L.pl_scl_decode,
@@ -86,7 +88,7 @@ def _declare(L):
               L.pl_awgn_qpsk_llr_bits, L.pl_sc_decode_count, L.pl_sc_sim_count, L.pl_clock_probe,
               L.pl_hybrid_decode, L.pl_crc_status, L.pl_nr_awgn_qpsk_llr, L.pl_count_errors_packed,
               L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr, L.pl_osd_plan_create, L.pl_osd_plan_destroy,
-              L.pl_osd_plan_info, L.pl_osd_decode, L.pl_genie_count):
+              L.pl_osd_plan_info, L.pl_osd_decode, L.pl_genie_count, L.pl_bp_decode):
         f.restype = ctypes.c_int
     return L
 
@@ -126,7 +128,7 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_hybrid_workspace_size", "pl_hybrid_decode", "pl_crc_status",
                     "pl_nr_awgn_qpsk_llr", "pl_count_errors_packed", "pl_awgn_qam_llr", "pl_nr_awgn_qam_llr",
                     "pl_osd_plan_create", "pl_osd_plan_destroy", "pl_osd_plan_info", "pl_osd_decode",
-                    "pl_genie_count", "pl_last_error_string", "pl_version")
+                    "pl_genie_count", "pl_bp_decode", "pl_last_error_string", "pl_version")
 
 
 class PolarArgumentError(PolarLibError, ValueError):

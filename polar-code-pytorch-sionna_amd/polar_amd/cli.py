@@ -19,6 +19,8 @@ scl leg dec_type="SCL" with --list_size (and --hybrid_sc), the LLRs from the fus
 'osd' in --algos adds the ordered-statistics decoder of order --osd_t (OSDecoder, my_sn/fec/osd/dec.py), the
 estimate of the maximum-likelihood curve: its BLER is comparable with SC / SCL (the encoder is injective), its
 BER counts codeword bits.
+'bp' in --algos adds the belief-propagation decoder (BP_Dec, pl_bp_decode): --bp_iter iterations of --bp_f
+(exact or minsum, the latter scaled by --bp_scale), --bp_early_stop ends a row once its decisions re-encode.
 """
 import argparse
 import math
@@ -69,7 +71,22 @@ def parse(argv=None):
     ap.add_argument("--design_rows", type=int, default=2 ** 20, help="--frozen design: codewords of the design run")
     ap.add_argument("--osd_t", type=int, default=2,
                     help="order of the OSD leg ('osd' in --algos): 0 <= t <= min(k, 4), at most 2^22 patterns")
+    ap.add_argument("--bp_iter", type=int, default=20, help="iterations of the BP leg ('bp' in --algos)")
+    ap.add_argument("--bp_f", choices=["exact", "minsum"], default="exact", help="f of the BP leg")
+    ap.add_argument("--bp_scale", type=float, default=1.0, help="BP leg, --bp_f minsum: the magnitude scale in (0, 1]")
+    ap.add_argument("--bp_early_stop", action="store_true",
+                    help="BP leg: a row stops once its hard decisions re-encode to those on the code bits")
     c = ap.parse_args(argv)
+    if "bp" in c.algos:
+        from .bp import BP_MAX_N
+        if c.code != "plain":
+            ap.error("'bp' in --algos needs --code plain")
+        if c.n > BP_MAX_N:
+            ap.error(f"'bp' in --algos needs --n <= {BP_MAX_N}")
+        if c.bp_iter < 1:
+            ap.error("--bp_iter must be >= 1")
+        if not 0.0 < c.bp_scale <= 1.0 or (c.bp_f == "exact" and c.bp_scale != 1.0):
+            ap.error("--bp_scale must be in (0, 1], and 1 with --bp_f exact")
     if "osd" in c.algos:
         from .osd import check_supported
         if c.code != "plain":
@@ -162,6 +179,10 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
     elif mode == "osd":  # decides codewords: the model compares them with the transmitted ones
         from .osd import OSDecoder
         dec = OSDecoder(c.osd_t, enc, device=dev_str)
+    elif mode == "bp":
+        from .bp import BP_Dec
+        dec = BP_Dec(fp, c.n, num_iter=c.bp_iter, device=dev_str, f=c.bp_f, scale=c.bp_scale,
+                     early_stop=c.bp_early_stop)
     else:
         raise Exception('error...')
     cw = mode == "osd"
@@ -203,6 +224,8 @@ def main(argv=None):
         codes.append(gen_code(c, f"SCL-{c.list_size}", "scl", device, gen))
     if "osd" in c.algos:
         codes.append(gen_code(c, f"OSD-{c.osd_t} (codeword BER)", "osd", device, gen))
+    if "bp" in c.algos:
+        codes.append(gen_code(c, f"BP-{c.bp_iter} ({c.bp_f})", "bp", device, gen))
     plot = PlotBER(f"Performance of Short Len Codes (k={c.k}, n={c.n})")
     results = {}
     for model, name in codes:

@@ -51,6 +51,9 @@ size_t scl_tree_workspace_size(const pl_plan* plan, int64_t bs);
 // PL_OK when the stream (NULL: the current device) is on the plan's device, else PL_EINVAL; capi.cpp
 int check_device(const pl_plan* plan, hipStream_t stream, const char* what);
 int launch_encode(const pl_plan* plan, const float* u, int64_t bs, float* cw, hipStream_t stream);
+// belief propagation (bp_kernel.hip); pl_bp_decode has checked the arguments
+int launch_bp(const pl_plan* plan, const float* llr, int64_t bs, int num_iter, float scale, int early_stop,
+              void* out_bits, int out_kind, float* soft_u, float* ext_x, int32_t* iters, hipStream_t stream);
 
 // Code-specialised SC kernels (jit.cpp)
 int attach_static(pl_plan* plan, const uint8_t* frozen_mask, bool allow_compile);
