@@ -37,6 +37,7 @@
  *   pl_osd_decode    OSDecoder.forward  my_sn/fec/osd/dec.py:148-192 (_find_mrb :107-147, _find_min_dist :82-106)
  *   pl_bp_decode     the "iterative BP decoding" of my_sn/fec/polar/dec.py:1 and Polar5GDecoder's
  *                    dec_type "BP" (named there, not implemented)
+ *   pl_scf_decode    no reference counterpart (CRC-aided SC-Flip; the contract is stated below)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -401,6 +402,42 @@ int pl_genie_count(int32_t n, int32_t f_mode, float llr_max, const float* llr_lo
 int pl_bp_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, int32_t num_iter, float scale,
                  uint32_t flags, void* out_bits, int32_t out_kind, float* soft_u, float* ext_x, int32_t* iters,
                  void* hip_stream);
+
+/* CRC-aided successive-cancellation flip decoding (SC-Flip; Afisiadis, Balatsoukas-Stimming, Burg 2014;
+ * polar_amd.SCF_Dec; csrc/scf_kernel.hip).  The reference has no such decoder.  SC first; a row whose SC
+ * result fails the CRC is decoded again with its least reliable decision inverted, one bit per attempt.
+ * plan: a list-size-1 plan (PL_EINVAL for a list plan) with a CRC (pl_plan_set_crc; PL_ENOTSUP without, as
+ * pl_crc_status); its n, frozen set, f_mode, llr_max and SC kernel are used.  2 <= n <= 1024; n = 2048 is
+ * PL_ENOTSUP.  llr_logits [bs, n] fp32 logits log P(1)/P(0); a = -logit.  f and g are pl_sc_decode's for the
+ * plan, HD(x) = !(x > 0), frozen positions decide 0, a row "passes" iff pl_crc_status of its k bits is 1.
+ * One row, T = max_flips (0 <= max_flips <= 64), T' = min(T, k):
+ *   attempt 0: u^0 = the row pl_sc_decode returns for this plan, bit for bit (it is launched).  If it
+ *     passes: out = u^0, crc_ok = 1, flip_pos = -1, attempts = 1.
+ *   candidates: alpha_i = the fp32 LLR at leaf i on which attempt 0 decided position i -- what
+ *     pl_genie_count's leaf_out[i] is when u_bits is u^0 over all n positions.  c_1 .. c_T' are the
+ *     information positions in ascending (|alpha_i|, i) order: magnitudes compared as fp32 values, +0 and -0
+ *     equal, the lower index first among equal magnitudes (min-sum gives many exact ties).
+ *   attempt t = 1 .. T': SC from the same logits, leaf by leaf, with the attempt's own feedback, except that
+ *     the decision at c_t is 1 - HD(alpha) of the attempt's own leaf LLR (which equals attempt 0's there).
+ *     The smallest t that passes gives out, crc_ok = 1, flip_pos = c_t (a u-domain position, 0 .. n-1),
+ *     attempts = 1 + t.  If none passes: out = u^0, crc_ok = 0, flip_pos = -1, attempts = 1 + T'.
+ * attempts is the number of SC decodes the sequential algorithm runs; the kernel runs several attempts of a
+ * row side by side and keeps the first that passes, which gives the same outputs.
+ * max_flips = 0 is pl_sc_decode plus pl_crc_status (attempts = 1); values above k behave as k.
+ * out_bits [bs, k], PL_OUT_F32 / PL_OUT_U8.  crc_ok [bs] bytes, flip_pos [bs] int32, attempts [bs] int32:
+ * each nullable.
+ * workspace: device scratch of pl_scf_workspace_size(plan, bs, max_flips) bytes, required: 5 bytes per row
+ * for the CRC flags and the list of failing rows, sized for every row failing, and 4.25 KiB of counters.
+ * No allocation per call and NO host synchronisation: the number of failing rows stays on the device, the
+ * second stage runs a fixed grid that strides over it, and the call can be captured into a HIP graph.
+ * bs == 0 is PL_OK.  PL_EINVAL (the message names the argument): a NULL or list plan, max_flips outside
+ * [0, 64], bs negative or >= 2^31, an unknown out_kind, a NULL llr_logits or out_bits with bs > 0, a NULL or
+ * short workspace, a stream of another device.  Every check but the last runs before any HIP call.
+ * NaN inputs are not supported. */
+size_t pl_scf_workspace_size(const pl_plan* plan, int64_t bs, int32_t max_flips);
+int pl_scf_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, int32_t max_flips, void* out_bits,
+                  int32_t out_kind, uint8_t* crc_ok, int32_t* flip_pos, int32_t* attempts, void* workspace,
+                  size_t ws_bytes, void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

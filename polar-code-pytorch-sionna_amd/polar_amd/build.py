@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libpolar_mi355x.so")
 KCACHE = os.path.join(HERE, "kcache")
 SOURCES = ["sc_kernel.hip", "scl_kernel.hip", "encode_kernel.hip", "ratematch_kernel.hip", "channel_kernel.hip",
            "clock_kernel.hip", "hybrid_kernel.hip", "osd_kernel.hip", "genie_kernel.hip", "bp_kernel.hip",
-           "capi.cpp", "jit.cpp"]
+           "scf_kernel.hip", "capi.cpp", "jit.cpp"]
 # scl_tree_kernel.hip is compiled once per list size (its instantiations, in parallel) and once
 # for the launcher: (object name, source, defines)
 UNITS = [(s + ".o", s, []) for s in SOURCES] + \
@@ -124,7 +124,7 @@ def build(force=False, verbose=False, dev=False):
     hash_h = _write_src_hash(obj_dir)
     deps = [os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "butterfly.h"), os.path.join(CSRC, "softplus.h"),
             os.path.join(CSRC, "exactf.h"),
-            os.path.join(CSRC, "hybrid.h"), os.path.join(CSRC, "osd.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
+            os.path.join(CSRC, "hybrid.h"), os.path.join(CSRC, "osd.h"), os.path.join(CSRC, "scf.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
     jobs = []
     for oname, s, defs in UNITS:
         src = os.path.join(CSRC, s)
@@ -230,7 +230,7 @@ def root_half_codes():
 # mother codes are decoded by the exact-f SC kernel (Polar5GDecoder dec_type="SC")
 POLAR5G_TEST_CODES = [(12, 20), (12, 160), (16, 64), (19, 100), (20, 40), (24, 300), (32, 64), (40, 100), (48, 64),
                       (64, 128), (64, 200), (100, 180), (120, 1000), (140, 576), (200, 400), (250, 300),
-                      (300, 1088), (500, 1024), (512, 700), (1013, 1088), (30, 1088), (64, 1024)]
+                      (300, 1088), (500, 1024), (512, 700), (1013, 1088), (30, 1088), (64, 1024), (40, 128)]
 
 
 def polar5g_codes():

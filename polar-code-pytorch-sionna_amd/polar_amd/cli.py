@@ -21,6 +21,8 @@ estimate of the maximum-likelihood curve: its BLER is comparable with SC / SCL (
 BER counts codeword bits.
 'bp' in --algos adds the belief-propagation decoder (BP_Dec, pl_bp_decode): --bp_iter iterations of --bp_f
 (exact or minsum, the latter scaled by --bp_scale), --bp_early_stop ends a row once its decisions re-encode.
+'scf' in --algos adds the CRC-aided SC-Flip decoder (SCF_Dec, pl_scf_decode) with --scf_flips candidate
+positions a row and the f of --scf_f; it needs --code 5g, the only code here with a CRC.
 """
 import argparse
 import math
@@ -76,7 +78,16 @@ def parse(argv=None):
     ap.add_argument("--bp_scale", type=float, default=1.0, help="BP leg, --bp_f minsum: the magnitude scale in (0, 1]")
     ap.add_argument("--bp_early_stop", action="store_true",
                     help="BP leg: a row stops once its hard decisions re-encode to those on the code bits")
+    ap.add_argument("--scf_flips", type=int, default=16,
+                    help="SC-Flip leg ('scf' in --algos): candidate positions a row, 0 ... 64")
+    ap.add_argument("--scf_f", choices=["exact", "minsum"], default="exact", help="f of the SC-Flip leg")
     c = ap.parse_args(argv)
+    if "scf" in c.algos:
+        from .scf import SCF_MAX_FLIPS
+        if c.code != "5g":
+            ap.error("'scf' in --algos needs --code 5g (the SC-Flip decoder needs the CRC)")
+        if not 0 <= c.scf_flips <= SCF_MAX_FLIPS:
+            ap.error(f"--scf_flips must be in [0, {SCF_MAX_FLIPS}]")
     if "bp" in c.algos:
         from .bp import BP_MAX_N
         if c.code != "plain":
@@ -140,6 +151,8 @@ def gen_code_5g(c, name, mode, device, generator=None):
         dec = Polar5GDecoder(enc, dec_type="SC")
     elif mode == "scl":
         dec = Polar5GDecoder(enc, dec_type="SCL", list_size=c.list_size, hybrid_sc=c.hybrid_sc)
+    elif mode == "scf":
+        dec = Polar5GDecoder(enc, dec_type="SCF", list_size=c.scf_flips, scf_f=c.scf_f)
     else:
         raise Exception('error...')
     if c.llr_producer == "fused":
@@ -226,6 +239,8 @@ def main(argv=None):
         codes.append(gen_code(c, f"OSD-{c.osd_t} (codeword BER)", "osd", device, gen))
     if "bp" in c.algos:
         codes.append(gen_code(c, f"BP-{c.bp_iter} ({c.bp_f})", "bp", device, gen))
+    if "scf" in c.algos:
+        codes.append(gen_code(c, f"SCF-{c.scf_flips} ({c.scf_f})", "scf", device, gen))
     plot = PlotBER(f"Performance of Short Len Codes (k={c.k}, n={c.n})")
     results = {}
     for model, name in codes:

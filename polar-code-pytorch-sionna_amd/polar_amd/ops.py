@@ -144,6 +144,61 @@ def hybrid_decode(sc_plan, scl_plan, llr_logits, out=None, out_dtype=torch.float
     return out, ok != 0, rows[: n_list.value], int(n_list.value)
 
 
+_scf_ws = {}  # (device, stream) -> the last SC-Flip workspace used there (grown, never shrunk)
+
+
+def scf_workspace(plan, bs, max_flips, device):
+    """A device workspace of pl_scf_workspace_size(plan, bs, max_flips) bytes, cached per device and
+    stream like hybrid_workspace: calls on one stream reuse it, a larger batch replaces it."""
+    ws_bytes = int(_lib.lib().pl_scf_workspace_size(plan.handle, bs, int(max_flips)))
+    device = torch.device(device)
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _scf_ws.get(key)
+    if ws is None or ws.numel() < ws_bytes:
+        ws = _scf_ws[key] = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def scf_decode(plan, llr_logits, max_flips, out=None, out_dtype=torch.float32, return_info=False):
+    """CRC-aided SC-Flip decode (pl_scf_decode) of [bs, n] fp32 logits -> [bs, k] bits: SC, then a row
+    whose result fails the plan's CRC (Plan.set_crc) is decoded again with the decision at each of its
+    max_flips (0 ... 64) least reliable information positions inverted in turn, until the CRC passes.
+    return_info: also (crc_ok bool [bs]; flip_pos int32 [bs], the inverted position 0 ... n-1 or -1;
+    attempts int32 [bs], the SC decodes the sequential algorithm runs).  No host synchronisation: with
+    `out` given and return_info False the call allocates nothing and can be captured (LaunchGraph)."""
+    _require_cuda(llr_logits, "llr_logits")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != plan.n:
+        raise ValueError(f"llr_logits must be [bs, {plan.n}], got {tuple(x.shape)}")
+    max_flips = int(max_flips)
+    if not 0 <= max_flips <= 64:
+        raise ValueError(f"max_flips must be in [0, 64], got {max_flips}")
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.k), dtype=out_dtype, device=x.device)
+    elif out.shape != (bs, plan.k) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+    ok = torch.empty((bs,), dtype=torch.uint8, device=x.device) if return_info else None
+    pos = torch.empty((bs,), dtype=torch.int32, device=x.device) if return_info else None
+    att = torch.empty((bs,), dtype=torch.int32, device=x.device) if return_info else None
+    L = _lib.lib()
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None and bs > 0 else 0)
+    with torch.cuda.device(x.device):
+        ws = scf_workspace(plan, bs, max_flips, x.device)
+        ws_bytes = int(L.pl_scf_workspace_size(plan.handle, bs, max_flips))
+        _lib.check(L.pl_scf_decode(plan.handle, ptr(x), bs, max_flips, ptr(out), kind, ptr(ok), ptr(pos), ptr(att),
+                                   ctypes.c_void_p(ws.data_ptr()), ws_bytes, _lib.current_stream_ptr(x.device)),
+                   "pl_scf_decode")
+    if not return_info:
+        return out
+    return out, ok != 0, pos, att
+
+
 def crc_status(plan, bits):
     """pl_crc_status: [bs, k] decoded bits (fp32 0/1 or uint8) -> bool [bs], True where the row
     passes the CRC of the plan (pl_plan_set_crc; the last `degree` bits are the parity)."""

@@ -382,17 +382,19 @@ class Polar5GEncoder(PolarEncoder):
 
 
 class Polar5GDecoder(nn.Module):
-    """5G NR polar decoder: rate recovery + SC / CRC-aided SCL + CRC removal (dec.py:539-666)."""
+    """5G NR polar decoder: rate recovery + SC / CRC-aided SCL + CRC removal (dec.py:539-666).
+    dec_type="SCF" (no reference counterpart): the mother decoder is the CRC-aided SC-Flip decoder
+    polar_amd.SCF_Dec with the encoder's CRC, list_size read as max_flips (0 ... 64) and f = scf_f."""
 
     def __init__(self, enc_polar, dec_type="SC", list_size=8, return_crc_status=False, output_dtype=tc.float32,
-                 hybrid_sc=False):
+                 hybrid_sc=False, scf_f="exact"):
         """hybrid_sc (no reference counterpart; dec_type="hybSCL" cannot be constructed there or here):
         with dec_type="SCL", the mother decoder is mysn.SCL_Dec(..., use_hybrid_sc=True) -- SC first,
         the list decoder only on the rows whose CRC fails."""
         super().__init__()
         assert isinstance(enc_polar, Polar5GEncoder), "enc_polar must be a Polar5GEncoder."
-        if hybrid_sc and dec_type == "SC":
-            raise ValueError("hybrid_sc needs dec_type='SCL' (the SC decoder has no list stage).")
+        if hybrid_sc and dec_type in ("SC", "SCF"):
+            raise ValueError("hybrid_sc needs dec_type='SCL' (the SC and SC-Flip decoders have no list stage).")
         self._output_dtype = output_dtype
         self._n_target, self._k_target = enc_polar.n_target, enc_polar.k_target
         self._n_polar, self._k_polar = enc_polar.n_polar, enc_polar.k_polar
@@ -410,6 +412,10 @@ class Polar5GDecoder(nn.Module):
             self._polar_dec = mysn.SCL_Dec(enc_polar._frozen_pos, self._n_polar,
                                            crc_degree=enc_polar.enc_crc.crc_degree, list_size=list_size,
                                            use_hybrid_sc=bool(hybrid_sc))
+        elif dec_type == "SCF":  # no reference counterpart: CRC-aided SC-Flip, list_size read as max_flips
+            from .scf import SCF_Dec
+            self._polar_dec = SCF_Dec(enc_polar._frozen_pos, self._n_polar, enc_polar.enc_crc.crc_degree,
+                                      max_flips=list_size, f=scf_f)
         elif dec_type == "hybSCL":
             raise NotImplementedError("hybSCL: the reference cannot construct it (dec.py:587-590)")
         else:
