@@ -38,6 +38,8 @@
  *   pl_bp_decode     the "iterative BP decoding" of my_sn/fec/polar/dec.py:1 and Polar5GDecoder's
  *                    dec_type "BP" (named there, not implemented)
  *   pl_scf_decode    no reference counterpart (CRC-aided SC-Flip; the contract is stated below)
+ *   pl_llr_quantize / pl_scq_decode: no reference counterpart (fixed-point SC on int8 LLRs; the contract
+ *                    is stated below)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -438,6 +440,39 @@ size_t pl_scf_workspace_size(const pl_plan* plan, int64_t bs, int32_t max_flips)
 int pl_scf_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, int32_t max_flips, void* out_bits,
                   int32_t out_kind, uint8_t* crc_ok, int32_t* flip_pos, int32_t* attempts, void* workspace,
                   size_t ws_bytes, void* hip_stream);
+
+/* Fixed-point successive-cancellation decoding on int8 LLRs, and the quantiser that produces them
+ * (polar_amd.SCQ_Dec; csrc/scq_kernel.hip).  The reference has no such decoder: it answers how many LLR bits a
+ * hardware SC decoder needs.  Everything is integer arithmetic, so the outputs equal the numpy restatement
+ * tests/golden/scq_ref.py bit for bit on every input.
+ * Cmax = 2^(q_channel-1) - 1, Imax = 2^(q_internal-1) - 1, 2 <= q_channel <= q_internal <= 8 (each function
+ * checks the width it is given; the order between the two is the caller's to keep: the decoder clamps what it
+ * loads to +-Imax either way).
+ *
+ * pl_llr_quantize: llr_logits [count] fp32 logits log P(1)/P(0) (pl_sc_decode's sign convention; the quantiser
+ * does not negate, the decoder does), count a number of elements, so any row length is served.
+ *   t = logit * inv_step (one fp32 rounding), q = rint(med3(t, -Cmax, Cmax)) with ties to even, stored as int8
+ *   in out_q [count].  +-Inf saturates to +-Cmax; NaN is not supported.  count == 0 is PL_OK.
+ * pl_scq_decode: plan is a list-size-1 plan of which only n and the frozen set are used (f_mode and llr_max are
+ * ignored, and the specialised SC kernel is never involved), 2 <= n <= 2048.  llr_q [bs, n] int8, any value
+ * including -128; 16-byte aligned when n >= 16 (the rows are read 16 LLRs at a time).  out_bits [bs, k],
+ * PL_OUT_F32 / PL_OUT_U8, information positions ascending, as pl_sc_decode.
+ *   load:  a_i = -clamp(llr_q_i, -Imax, Imax)            (positive favours 0, as in the float kernels)
+ *   f(x, y) = sgn(x) sgn(y) min(|x|, |y|), sgn(0) = 0    (the range is symmetric: no overflow)
+ *   g(x, y, b) = clamp(y + (1 - 2b) x, -Imax, Imax)
+ *   leaf:  a frozen position decides 0, any other HD(a) = !(a > 0), so 0 decides 1 (polar_sc.py:94-97)
+ *   partial sums and order: the plain SC recursion, the left child on f, the right child on g with the left
+ *   child's re-encoded bits.
+ * No allocation per call and no host synchronisation: both calls can be captured into a HIP graph.  bs == 0 is
+ * PL_OK.  PL_EINVAL (the message names the argument): a NULL or list plan, q_channel or q_internal outside
+ * [2, 8], a negative bs or count, an unknown out_kind, a NULL (or, for llr_q, misaligned) buffer with bs > 0 or
+ * count > 0, an inv_step that is not positive and finite, a stream of another device than the plan's
+ * (pl_llr_quantize has no plan: its stream and buffers are the caller's to keep on one device).  Every check but
+ * the last runs before any HIP call. */
+int pl_llr_quantize(const float* llr_logits, int64_t count, float inv_step, int32_t q_channel, int8_t* out_q,
+                    void* hip_stream);
+int pl_scq_decode(const pl_plan* plan, const int8_t* llr_q, int64_t bs, int32_t q_internal, void* out_bits,
+                  int32_t out_kind, void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

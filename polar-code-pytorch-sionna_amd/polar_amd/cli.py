@@ -23,6 +23,8 @@ BER counts codeword bits.
 (exact or minsum, the latter scaled by --bp_scale), --bp_early_stop ends a row once its decisions re-encode.
 'scf' in --algos adds the CRC-aided SC-Flip decoder (SCF_Dec, pl_scf_decode) with --scf_flips candidate
 positions a row and the f of --scf_f; it needs --code 5g, the only code here with a CRC.
+'scq' in --algos adds the fixed-point SC decoder (SCQ_Dec, pl_llr_quantize + pl_scq_decode): channel LLRs of
+--scq_qc bits with the largest level at --scq_llr_max, internal LLRs of --scq_qi bits; --code plain only.
 """
 import argparse
 import math
@@ -81,7 +83,19 @@ def parse(argv=None):
     ap.add_argument("--scf_flips", type=int, default=16,
                     help="SC-Flip leg ('scf' in --algos): candidate positions a row, 0 ... 64")
     ap.add_argument("--scf_f", choices=["exact", "minsum"], default="exact", help="f of the SC-Flip leg")
+    ap.add_argument("--scq_qc", type=int, default=6, help="fixed-point SC leg ('scq' in --algos): channel LLR bits, 2 ... 8")
+    ap.add_argument("--scq_qi", type=int, default=6,
+                    help="fixed-point SC leg: internal LLR bits, --scq_qc ... 8")
+    ap.add_argument("--scq_llr_max", type=float, default=30.0,
+                    help="fixed-point SC leg: the logit magnitude of the largest channel level")
     c = ap.parse_args(argv)
+    if "scq" in c.algos:
+        if c.code != "plain":
+            ap.error("'scq' in --algos needs --code plain")
+        if not 2 <= c.scq_qc <= c.scq_qi <= 8:
+            ap.error("--scq_qc and --scq_qi must satisfy 2 <= scq_qc <= scq_qi <= 8")
+        if not (c.scq_llr_max > 0.0 and math.isfinite(c.scq_llr_max)):
+            ap.error("--scq_llr_max must be positive and finite")
     if "scf" in c.algos:
         from .scf import SCF_MAX_FLIPS
         if c.code != "5g":
@@ -196,6 +210,9 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
         from .bp import BP_Dec
         dec = BP_Dec(fp, c.n, num_iter=c.bp_iter, device=dev_str, f=c.bp_f, scale=c.bp_scale,
                      early_stop=c.bp_early_stop)
+    elif mode == "scq":
+        from .quant import SCQ_Dec
+        dec = SCQ_Dec(fp, c.n, q_channel=c.scq_qc, q_internal=c.scq_qi, llr_max=c.scq_llr_max, device=dev_str)
     else:
         raise Exception('error...')
     cw = mode == "osd"
@@ -241,6 +258,8 @@ def main(argv=None):
         codes.append(gen_code(c, f"BP-{c.bp_iter} ({c.bp_f})", "bp", device, gen))
     if "scf" in c.algos:
         codes.append(gen_code(c, f"SCF-{c.scf_flips} ({c.scf_f})", "scf", device, gen))
+    if "scq" in c.algos:
+        codes.append(gen_code(c, f"SCQ ({c.scq_qc},{c.scq_qi})", "scq", device, gen))
     plot = PlotBER(f"Performance of Short Len Codes (k={c.k}, n={c.n})")
     results = {}
     for model, name in codes:

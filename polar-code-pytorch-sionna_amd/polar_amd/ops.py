@@ -199,6 +199,66 @@ def scf_decode(plan, llr_logits, max_flips, out=None, out_dtype=torch.float32, r
     return out, ok != 0, pos, att
 
 
+def _width(q, name):
+    try:
+        v = q.__index__()  # Python and numpy integers, no floats
+    except (AttributeError, TypeError):
+        v = None
+    if v is None or isinstance(q, bool) or not 2 <= v <= 8:
+        raise ValueError(f"{name} must be an integer in [2, 8], got {q!r}")
+    return v
+
+
+def llr_quantize(llr_logits, inv_step, q_channel, out=None):
+    """Quantise fp32 logits of any shape to int8 (pl_llr_quantize): q = rint(clamp(logit * inv_step, -Cmax, Cmax)),
+    ties to even, Cmax = 2^(q_channel-1) - 1; +-Inf saturates.  The sign is kept (the decoder negates).  `out`:
+    a contiguous int8 tensor of the input's shape on its device (then nothing is allocated)."""
+    _require_cuda(llr_logits, "llr_logits")
+    q_channel = _width(q_channel, "q_channel")
+    inv_step = float(inv_step)
+    if not (inv_step > 0.0 and inv_step != float("inf")):
+        raise ValueError(f"inv_step must be positive and finite, got {inv_step}")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+    elif out.dtype != torch.int8 or out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous int8 tensor of the input's shape on the input's device")
+    count = x.numel()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_llr_quantize(ctypes.c_void_p(x.data_ptr() if count else 0), count, inv_step, q_channel,
+                                              ctypes.c_void_p(out.data_ptr() if count else 0),
+                                              _lib.current_stream_ptr(x.device)), "pl_llr_quantize")
+    return out
+
+
+def scq_decode(plan, llr_q, q_internal, out=None, out_dtype=torch.float32):
+    """Fixed-point SC decode (pl_scq_decode) of [bs, n] int8 LLRs (logit sign, any value) -> [bs, k] bits, all
+    node values integers clamped to +-(2^(q_internal-1) - 1).  Only the plan's n and frozen set are used.  With
+    `out` given nothing is allocated and the call can be captured (LaunchGraph)."""
+    _require_cuda(llr_q, "llr_q")
+    q_internal = _width(q_internal, "q_internal")
+    x = llr_q
+    if x.dtype != torch.int8:
+        raise ValueError(f"llr_q must be an int8 tensor (llr_quantize), got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] != plan.n:
+        raise ValueError(f"llr_q must be [bs, {plan.n}], got {tuple(x.shape)}")
+    if not x.is_contiguous() or x.data_ptr() % 16:  # the kernel reads a row 16 bytes at a time
+        x = x.clone(memory_format=torch.contiguous_format)
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.k), dtype=out_dtype, device=x.device)
+    elif out.shape != (bs, plan.k) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_scq_decode(plan.handle, ctypes.c_void_p(x.data_ptr() if bs else 0), bs, q_internal,
+                                            ctypes.c_void_p(out.data_ptr() if bs else 0), kind,
+                                            _lib.current_stream_ptr(x.device)), "pl_scq_decode")
+    return out
+
+
 def crc_status(plan, bits):
     """pl_crc_status: [bs, k] decoded bits (fp32 0/1 or uint8) -> bool [bs], True where the row
     passes the CRC of the plan (pl_plan_set_crc; the last `degree` bits are the parity)."""
