@@ -226,6 +226,104 @@ def root_half_codes():
     return out
 
 
+ZOO_NS = (64, 128, 256, 512, 1024, 2048)
+# sibling pairs [left | right] of equal size >= 4 whose parent is a general node: between them every
+# type is once a left and once a right child, and the SPC right child has a rate-0 left sibling (its
+# input is then the plain sum x + y of the parent's halves, so it can exceed llr_max below a left turn)
+ZOO_PAIRS = (("R0", "SPC"), ("SPC", "REP"), ("R1", "R0"), ("REP", "R1"))
+# size-2 nodes next to a size-2 filler (two size-2 shortcut nodes side by side are a size-4 one)
+ZOO_SMALL = (("R0", "FILL"), ("FILL", "R1"), ("REP", "FILL"), ("FILL", "R0"), ("R1", "FILL"), ("FILL", "REP"),
+             ("REP", "FILL"), ("FILL", "R1"))
+
+
+def node_type(block):
+    """Type of the node over the frozen flags `block` (csrc/jit.cpp node_types: a size-2 node with
+    only its first position frozen is REP, which is tested before SPC)."""
+    size, nfz = len(block), int(sum(int(b) != 0 for b in block))
+    if nfz == size:
+        return "R0"
+    if nfz == 0:
+        return "R1"
+    if size >= 2 and nfz == size - 1 and not block[-1]:
+        return "REP"
+    if size >= 2 and nfz == 1 and block[0]:
+        return "SPC"
+    return "GEN"
+
+
+def _zoo_block(kind, size):
+    import numpy as np
+    if kind == "R0":
+        return np.ones(size, np.uint8)
+    if kind == "R1":
+        return np.zeros(size, np.uint8)
+    if kind == "REP":
+        return np.r_[np.ones(size - 1, np.uint8), np.uint8(0)]
+    if kind == "SPC":
+        return np.r_[np.uint8(1), np.zeros(size - 1, np.uint8)]
+    assert kind == "FILL"  # information first, frozen last: a general node at every size >= 2
+    return np.tile(np.array([0, 1], np.uint8), size // 2)
+
+
+def node_zoo():
+    """Min-sum frozen masks that plant every shortcut node type (rate-0, rate-1, repetition, SPC) at
+    every stage s = 1 ... log_n - 1 of n = 64 ... 2048 below general ancestors only, so the
+    shortcut under test is the code that runs (tests/test_sc_nodes_ref.py, test_sc_nodes_gpu.py).
+    At s >= 2 every type is once a left and once a right child (ZOO_PAIRS).  Seven codes per n:
+    six whose one root half is REP, SPC or rate-1 and whose other half is general, and one with two
+    general halves; the eight general halves hold one pair of stage log_n - 2 each (four of them) or
+    one pair of every stage 2 ... log_n - 3 and two size-2 nodes (the other four).
+    Returns [(name, mask, planted)], planted = [(s, q, type)]: the stage-s node at position q << s."""
+    import numpy as np
+    out = []
+    for n in ZOO_NS:
+        log_n, half = n.bit_length() - 1, n // 2
+        halves = []  # (mask of the half, [(s, offset in the half, type)])
+        for b in range(4):  # one pair of stage log_n - 2
+            s = log_n - 2
+            a, c = ZOO_PAIRS[b]
+            halves.append((np.r_[_zoo_block(a, 1 << s), _zoo_block(c, 1 << s)], [(s, 0, a), (s, 1 << s, c)]))
+        for b in range(4):  # one pair of every lower stage (largest first: aligned), two size-2 nodes
+            parts, nodes, off = [], [], 0
+            for s in range(log_n - 3, 1, -1):
+                a, c = ZOO_PAIRS[(b + s) % 4]
+                parts += [_zoo_block(a, 1 << s), _zoo_block(c, 1 << s)]
+                nodes += [(s, off, a), (s, off + (1 << s), c)]
+                off += 2 << s
+            for a, c in ZOO_SMALL[2 * b: 2 * b + 2]:
+                parts += [_zoo_block(a, 2), _zoo_block(c, 2)]
+                nodes += [(1, off + 2 * i, t) for i, t in enumerate((a, c)) if t != "FILL"]
+                off += 4
+            assert off == half
+            halves.append((np.concatenate(parts), nodes))
+        top, low = halves[:4], halves[4:]
+        layout = [("REP", top[0]), ("SPC", top[1]), ("R1", low[0]), (top[2], "REP"), (top[3], "SPC"), (low[1], "R1"),
+                  (low[2], low[3])]
+        for left, right in layout:
+            mask, planted = [], []
+            for side, h in enumerate((left, right)):
+                if isinstance(h, str):
+                    mask.append(_zoo_block(h, half))
+                    planted.append((log_n - 1, side, h))
+                else:
+                    mask.append(h[0])
+                    planted += [(s, (side * half + o) >> s, t) for s, o, t in h[1]]
+            mask = np.concatenate(mask).astype(np.uint8)
+            for s, q, t in planted:  # the type, and general ancestors up to the root
+                assert node_type(mask[q << s: (q + 1) << s]) == t, (n, s, q, t)
+                for up in range(s + 1, log_n + 1):
+                    p = (q << s) >> up << up
+                    assert node_type(mask[p: p + (1 << up)]) == "GEN", (n, s, q, t, up)
+            name = f"n{n}:" + ",".join(f"s{s}q{q}{t}" for s, q, t in planted)
+            out.append((name, mask, planted))
+    return out
+
+
+def node_zoo_codes():
+    """(name, mask) of the node zoo (node_zoo above); the name lists the planted (s, q, type)."""
+    return [(name, mask) for name, mask, _ in node_zoo()]
+
+
 # 5G NR (k, E) configurations the package's tests decode (tests/test_polar5g_gpu.py); their
 # mother codes are decoded by the exact-f SC kernel (Polar5GDecoder dec_type="SC")
 POLAR5G_TEST_CODES = [(12, 20), (12, 160), (16, 64), (19, 100), (20, 40), (24, 300), (32, 64), (40, 100), (48, 64),
@@ -270,6 +368,7 @@ def reference_codes():
         out += polar5g_codes()
     out += test_random_codes()
     out += [(m, 0) for _, m in root_half_codes()]
+    out += [(m, 0) for _, m in node_zoo_codes()]  # tests/test_sc_nodes_gpu.py
     # tests/test_sc_gpu.py::test_sc_edge_cases: n = 64 with every position frozen (k = 0) and none (k = n)
     out += [(np.ones(64, dtype=np.uint8), 0), (np.zeros(64, dtype=np.uint8), 0)]
     # tests/test_sc_gpu.py::test_sc_exact_large_llr_max_*: every n = 2, 4 code with k >= 1, exact f,
