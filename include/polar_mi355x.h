@@ -40,6 +40,7 @@
  *   pl_scf_decode    no reference counterpart (CRC-aided SC-Flip; the contract is stated below)
  *   pl_llr_quantize / pl_scq_decode: no reference counterpart (fixed-point SC on int8 LLRs; the contract
  *                    is stated below)
+ *   pl_ae_decode     no reference counterpart (automorphism-ensemble SC; the contract is stated below)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -473,6 +474,35 @@ int pl_llr_quantize(const float* llr_logits, int64_t count, float inv_step, int3
                     void* hip_stream);
 int pl_scq_decode(const pl_plan* plan, const int8_t* llr_q, int64_t bs, int32_t q_internal, void* out_bits,
                   int32_t out_kind, void* hip_stream);
+
+/* Automorphism-ensemble SC decoding (AED; Geiselhart, Elkelesh, Ebada, Cammerer, ten Brink 2021;
+ * polar_amd.AE_Dec; csrc/ae_kernel.hip).  The reference has no such decoder.  M permuted copies of the received
+ * word are decoded by plain SC, the M candidate codewords are un-permuted, and the one closest to the received
+ * word is kept.  It suits codes with a large automorphism group that SC is not invariant under: the
+ * Reed-Muller codes the row-weight frozen sets are whenever k is a sum of binomials.
+ * plan: a list-size-1 plan (PL_EINVAL for a list plan); its n, frozen set, f_mode and llr_max are used.
+ * 2 <= n <= 1024; n = 2048 is PL_ENOTSUP.  llr_logits [bs, n] fp32 logits log P(1)/P(0).
+ * perms: DEVICE memory, [num_perms][n] uint16, 1 <= num_perms <= 64; row t is a permutation pi_t of 0 .. n-1.
+ * The call cannot check device data: the kernel masks every entry with n - 1, so a bad table never indexes
+ * outside the row (the result is then unspecified, the accesses are not).
+ * One row, a = -logits:
+ *   candidate t: a'[i] = a[pi_t(i)].  a' is decoded by leaf-by-leaf SC exactly as an attempt of pl_scf_decode
+ *     with no inverted decision: f of the plan, g = (1 - 2 u) x + y in one rounding, HD(x) = !(x > 0), nodes of
+ *     nothing but frozen leaves decide 0, no repetition or parity-check shortcuts.  x' = the root's partial
+ *     sums (the codeword SC decided on); the candidate codeword is x_t[pi_t(i)] = x'[i].
+ *   metric: m_t = sum_i |a_i| [x_t[i] != HD(a_i)], accumulated in fp32; the order of the sum is not part of
+ *     the contract.  Zero LLRs contribute nothing either way.
+ *   winner: the t with the smallest fp32 metric as computed, the lowest t among equal fp32 values (the key
+ *     (bits of m_t) << 32 | t compared as an unsigned integer; metrics are non-negative).
+ * out_bits [bs, k], PL_OUT_F32 / PL_OUT_U8: (x_t* G_n) at the information positions.  best_idx [bs] int32 (t*)
+ * and best_metric [bs] fp32 (m_t*): each nullable.  The output is defined for any permutation table: a pi_t
+ * that is no automorphism of the code only makes a poor candidate.
+ * No workspace, no allocation, NO host synchronisation: one launch on the caller's stream, capturable into a
+ * HIP graph.  bs == 0 is PL_OK.  PL_EINVAL (the message names the argument): a NULL or list plan, num_perms
+ * outside [1, 64], bs negative, an unknown out_kind, a NULL llr_logits, perms or out_bits with bs > 0, a
+ * stream of another device.  Every check but the last runs before any HIP call.  NaN inputs are not supported. */
+int pl_ae_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, const uint16_t* perms, int32_t num_perms,
+                 void* out_bits, int32_t out_kind, int32_t* best_idx, float* best_metric, void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

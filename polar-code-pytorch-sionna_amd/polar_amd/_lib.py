@@ -84,6 +84,7 @@ def _declare(L):
     L.pl_scf_decode.argtypes = [P, P, i64, i32, P, i32, P, P, P, P, ctypes.c_size_t, P]
     L.pl_llr_quantize.argtypes = [P, i64, ctypes.c_float, i32, P, P]
     L.pl_scq_decode.argtypes = [P, P, i64, i32, P, i32, P]
+    L.pl_ae_decode.argtypes = [P, P, i64, P, i32, P, i32, P, P, P]
     L.pl_last_error_string.restype = ctypes.c_char_p
     L.pl_version.restype = ctypes.c_char_p
     for f in (L.pl_plan_create, L.pl_plan_destroy, L.pl_plan_info, L.pl_plan_device, L.pl_sc_decode, L.pl_scl_decode,
@@ -94,7 +95,7 @@ def _declare(L):
               L.pl_hybrid_decode, L.pl_crc_status, L.pl_nr_awgn_qpsk_llr, L.pl_count_errors_packed,
               L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr, L.pl_osd_plan_create, L.pl_osd_plan_destroy,
               L.pl_osd_plan_info, L.pl_osd_decode, L.pl_genie_count, L.pl_bp_decode, L.pl_scf_decode,
-              L.pl_llr_quantize, L.pl_scq_decode):
+              L.pl_llr_quantize, L.pl_scq_decode, L.pl_ae_decode):
         f.restype = ctypes.c_int
     return L
 
@@ -135,7 +136,7 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_nr_awgn_qpsk_llr", "pl_count_errors_packed", "pl_awgn_qam_llr", "pl_nr_awgn_qam_llr",
                     "pl_osd_plan_create", "pl_osd_plan_destroy", "pl_osd_plan_info", "pl_osd_decode",
                     "pl_genie_count", "pl_bp_decode", "pl_scf_workspace_size", "pl_scf_decode",
-                    "pl_llr_quantize", "pl_scq_decode",
+                    "pl_llr_quantize", "pl_scq_decode", "pl_ae_decode",
                     "pl_last_error_string", "pl_version")
 
 

@@ -23,6 +23,10 @@ BER counts codeword bits.
 (exact or minsum, the latter scaled by --bp_scale), --bp_early_stop ends a row once its decisions re-encode.
 'scf' in --algos adds the CRC-aided SC-Flip decoder (SCF_Dec, pl_scf_decode) with --scf_flips candidate
 positions a row and the f of --scf_f; it needs --code 5g, the only code here with a CRC.
+'ae' in --algos adds the automorphism-ensemble SC decoder (AE_Dec, pl_ae_decode): --ae_perms permuted SC
+decodes a row through bit-index (--ae_kind stage) or GL(m, 2) (--ae_kind linear) automorphisms of the code,
+with the f of --ae_f.  It pays on the Reed-Muller sets (k a sum of binomials, e.g. --k 64 --n 128); a frozen
+set that admits fewer than --ae_perms such permutations is an argument error.
 'scq' in --algos adds the fixed-point SC decoder (SCQ_Dec, pl_llr_quantize + pl_scq_decode): channel LLRs of
 --scq_qc bits with the largest level at --scq_llr_max, internal LLRs of --scq_qi bits; --code plain only.
 """
@@ -83,12 +87,26 @@ def parse(argv=None):
     ap.add_argument("--scf_flips", type=int, default=16,
                     help="SC-Flip leg ('scf' in --algos): candidate positions a row, 0 ... 64")
     ap.add_argument("--scf_f", choices=["exact", "minsum"], default="exact", help="f of the SC-Flip leg")
+    ap.add_argument("--ae_perms", type=int, default=8,
+                    help="automorphism-ensemble leg ('ae' in --algos): permuted SC decodes a row, 1 ... 64")
+    ap.add_argument("--ae_kind", choices=["stage", "linear"], default="stage",
+                    help="automorphism-ensemble leg: bit-index permutations or GL(m, 2) maps")
+    ap.add_argument("--ae_f", choices=["minsum", "exact"], default="minsum", help="f of the automorphism-ensemble leg")
     ap.add_argument("--scq_qc", type=int, default=6, help="fixed-point SC leg ('scq' in --algos): channel LLR bits, 2 ... 8")
     ap.add_argument("--scq_qi", type=int, default=6,
                     help="fixed-point SC leg: internal LLR bits, --scq_qc ... 8")
     ap.add_argument("--scq_llr_max", type=float, default=30.0,
                     help="fixed-point SC leg: the logit magnitude of the largest channel level")
     c = ap.parse_args(argv)
+    c._error = ap.error
+    if "ae" in c.algos:
+        from .ae import AE_MAX_N, AE_MAX_PERMS
+        if c.code != "plain":
+            ap.error("'ae' in --algos needs --code plain")
+        if c.n > AE_MAX_N:
+            ap.error(f"'ae' in --algos needs --n <= {AE_MAX_N}")
+        if not 1 <= c.ae_perms <= AE_MAX_PERMS:
+            ap.error(f"--ae_perms must be in [1, {AE_MAX_PERMS}]")
     if "scq" in c.algos:
         if c.code != "plain":
             ap.error("'scq' in --algos needs --code plain")
@@ -210,6 +228,12 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
         from .bp import BP_Dec
         dec = BP_Dec(fp, c.n, num_iter=c.bp_iter, device=dev_str, f=c.bp_f, scale=c.bp_scale,
                      early_stop=c.bp_early_stop)
+    elif mode == "ae":
+        from .ae import AE_Dec
+        try:  # the frozen set is known only here (--frozen design makes it on the GPU)
+            dec = AE_Dec(fp, c.n, num_perms=c.ae_perms, kind=c.ae_kind, seed=c.seed, f=c.ae_f, device=dev_str)
+        except ValueError as e:
+            c._error(f"'ae' in --algos: {e}")
     elif mode == "scq":
         from .quant import SCQ_Dec
         dec = SCQ_Dec(fp, c.n, q_channel=c.scq_qc, q_internal=c.scq_qi, llr_max=c.scq_llr_max, device=dev_str)
@@ -258,6 +282,8 @@ def main(argv=None):
         codes.append(gen_code(c, f"BP-{c.bp_iter} ({c.bp_f})", "bp", device, gen))
     if "scf" in c.algos:
         codes.append(gen_code(c, f"SCF-{c.scf_flips} ({c.scf_f})", "scf", device, gen))
+    if "ae" in c.algos:
+        codes.append(gen_code(c, f"AE-{c.ae_perms} ({c.ae_kind}, {c.ae_f})", "ae", device, gen))
     if "scq" in c.algos:
         codes.append(gen_code(c, f"SCQ ({c.scq_qc},{c.scq_qi})", "scq", device, gen))
     plot = PlotBER(f"Performance of Short Len Codes (k={c.k}, n={c.n})")

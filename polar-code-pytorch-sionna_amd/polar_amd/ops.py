@@ -259,6 +259,57 @@ def scq_decode(plan, llr_q, q_internal, out=None, out_dtype=torch.float32):
     return out
 
 
+def ae_perm_table(perms, device):
+    """[M, n] integer permutations (rows) -> the contiguous device table pl_ae_decode reads: uint16 values
+    carried in an int16 tensor (1 <= M <= 64, entries in [0, n), n <= 1024)."""
+    import numpy as np
+    p = np.asarray(perms.cpu() if isinstance(perms, torch.Tensor) else perms)
+    if p.ndim != 2 or not 1 <= p.shape[0] <= 64 or p.dtype.kind not in "iu":
+        raise ValueError(f"perms must be an [M, n] integer array with 1 <= M <= 64, got {p.dtype} {p.shape}")
+    if p.min() < 0 or p.max() >= p.shape[1]:
+        raise ValueError("perms: entries must be in [0, n)")
+    return torch.from_numpy(np.ascontiguousarray(p.astype(np.uint16)).view(np.int16)).to(device)
+
+
+def ae_decode(plan, llr_logits, perm_table, out=None, out_dtype=torch.float32, return_info=False):
+    """Automorphism-ensemble SC decode (pl_ae_decode) of [bs, n] fp32 logits -> [bs, k] bits: every row is
+    decoded by plain SC through each of the M permutations of perm_table (ae_perm_table: [M, n] on the
+    input's device) and the candidate codeword closest to the row is kept.  return_info: also (best_idx
+    int32 [bs], the winning candidate; best_metric fp32 [bs], its distance sum |a_i| [x_i != HD(a_i)]).
+    One launch, no workspace, no host synchronisation: with `out` given and return_info False the call
+    allocates nothing and can be captured (LaunchGraph)."""
+    _require_cuda(llr_logits, "llr_logits")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != plan.n:
+        raise ValueError(f"llr_logits must be [bs, {plan.n}], got {tuple(x.shape)}")
+    t = perm_table
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int16 or t.dim() != 2 or t.shape[1] != plan.n or \
+            not t.is_contiguous() or t.device != x.device:
+        raise ValueError("perm_table must be a contiguous int16 [M, n] tensor on the input's device (ae_perm_table)")
+    if not 1 <= t.shape[0] <= 64:
+        raise ValueError(f"perm_table must hold 1 ... 64 permutations, got {t.shape[0]}")
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.k), dtype=out_dtype, device=x.device)
+    elif out.shape != (bs, plan.k) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+    idx = torch.empty((bs,), dtype=torch.int32, device=x.device) if return_info else None
+    met = torch.empty((bs,), dtype=torch.float32, device=x.device) if return_info else None
+
+    def ptr(v):
+        return ctypes.c_void_p(v.data_ptr() if v is not None and bs > 0 else 0)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_ae_decode(plan.handle, ptr(x), bs, ctypes.c_void_p(t.data_ptr()), t.shape[0], ptr(out),
+                                           kind, ptr(idx), ptr(met), _lib.current_stream_ptr(x.device)),
+                   "pl_ae_decode")
+    if not return_info:
+        return out
+    return out, idx, met
+
+
 def crc_status(plan, bits):
     """pl_crc_status: [bs, k] decoded bits (fp32 0/1 or uint8) -> bool [bs], True where the row
     passes the CRC of the plan (pl_plan_set_crc; the last `degree` bits are the parity)."""
