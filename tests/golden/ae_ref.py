@@ -28,8 +28,9 @@ ROWS = 37
 FRAGILE_CAP = 4  # fragile rows (left out of the device comparison) of an exact-f case, of ROWS
 
 
-def ae_decode(logits, frozen_pos, n, perms, llr_max=30.0, exact=False):
-    """perms [M, n].  Returns a dict: bits [M, rows, k] uint8 (every candidate's information bits), metric
+def ae_decode(logits, frozen_pos, n, perms, llr_max=30.0, exact=False, tree=None):
+    """perms [M, n]; tree: scf_ref.sc_flip's false_r0 / bl0 switches (a deliberately wrong SC, for
+    tests/test_tree_zoo_ref.py).  Returns a dict: bits [M, rows, k] uint8 (every candidate's information bits), metric
     [M, rows] fp64, best_idx [rows] int32 (the first minimum of the fp64 metrics), fragile [rows] bool (exact f:
     some candidate's decode had an f too near a rounding midpoint to pin)."""
     x = np.ascontiguousarray(logits, dtype=F32)
@@ -40,7 +41,7 @@ def ae_decode(logits, frozen_pos, n, perms, llr_max=30.0, exact=False):
     info = np.setdiff1d(np.arange(n), fp)
     # all candidates as one batch of M * rows rows
     stacked = np.concatenate([x[:, pi] for pi in perms], axis=0)
-    u, _, fr = scf_ref.sc_flip(stacked, fp, n, np.full(m_tot * rows, -1), llr_max, exact)
+    u, _, fr = scf_ref.sc_flip(stacked, fp, n, np.full(m_tot * rows, -1), llr_max, exact, **(tree or {}))
     xp = scf_ref.encode(u).reshape(m_tot, rows, n)
     a = (F32(-1.0) * x).astype(np.float64)
     hd = genie_ref.hard(a)
@@ -85,6 +86,10 @@ def _table(spec, n, m_tot, kind):
         return automorphism.stage_permutations(fp, n, m_tot, seed=n + m_tot)
     if kind == "linear":
         return automorphism.linear_permutations(fp, n, m_tot, seed=n + m_tot)
+    if kind == "mixed":  # the identity, one bit-index permutation, one seeded random permutation (no automorphism)
+        m = n.bit_length() - 1
+        return np.stack([np.arange(n), automorphism.perm_table([1 << (m - 1 - b) for b in range(m)], n),
+                         np.random.default_rng(n + 1).permutation(n)])[:m_tot]
     assert kind == "random_first"  # the deliberate non-automorphism: a seeded random permutation, then the identity
     return np.stack([np.random.default_rng(n).permutation(n), np.arange(n)])
 
@@ -100,7 +105,9 @@ GRID_CASES = [
     ("g2", 2, "low:1", 1, "stage"),
     ("g4", 4, "low:1", 2, "stage"),
     ("g8_all6", 8, "rm:1", 6, "stage"),
+    ("g16_rm1_m8", 16, "rm:1", 8, "stage"),
     ("g32", 32, "rm:2", 8, "stage"),
+    ("g64_rm2_m64", 64, "rm:2", 64, "stage"),
     ("g128_m3", 128, "rm:3", 3, "stage"),
     ("g128_m64", 128, "rm:3", 64, "stage"),
     ("g256_m33", 256, "rm:3", 33, "stage"),
@@ -109,6 +116,9 @@ GRID_CASES = [
     ("g1024_m9", 1024, "rm:4", 9, "stage"),
     ("g1024_m64", 1024, "rm:4", 64, "stage"),
 ]
+# more rows than the kernel's 4096-block grid: rows 4096 and up are the second stride of a work-group that has
+# already used its LDS row and codeword buffers.  (case, rows)
+PAST_GRID_CASE = (("g8_past_grid", 8, "low:3", 3, "mixed"), 4099 + 37)
 NON_AUTOMORPHISM_CASE = ("g64_random", 64, "pin:32", 2, "random_first")
 AWGN_CASES = [
     ("a32", 32, "rm:2", 8, "stage", 4.0),
@@ -158,12 +168,12 @@ def exact_grid_llrs(seed, rows, n, frozen_pos=None):
     return (q / 8.0).astype(F32)
 
 
-def case_inputs(case):
-    """(frozen_pos, perms [M, n], logits [ROWS, n]) of a case: grid logits for the cases without an Eb/N0,
+def case_inputs(case, rows=ROWS):
+    """(frozen_pos, perms [M, n], logits [rows, n]) of a case: grid logits for the cases without an Eb/N0,
     seeded AWGN rows for those with one."""
     fp = frozen_of(case[2], case[1])
     if len(case) > 5:
-        _, x = awgn_rows(_seed(case), fp, case[1], ROWS, case[5])
+        _, x = awgn_rows(_seed(case), fp, case[1], rows, case[5])
     else:
-        x = exact_grid_llrs(_seed(case), ROWS, case[1], fp)
+        x = exact_grid_llrs(_seed(case), rows, case[1], fp)
     return fp, table_of(case), x

@@ -177,3 +177,22 @@ def early_stop_inputs(n, frozen_pos):
         parts.append(awgn_logits(rng, frozen_pos, n, 8, ebno_db)[1])
     parts.append((rng.standard_normal((6, n)) * 4).astype(F32))
     return np.concatenate(parts)
+
+
+# Early stop at every size of the two stop paths (n <= 64: several codewords a wave; n >= 128: the butterfly over
+# n / 32 words): the frozen set is rate_half_frozen(n, EARLY_STOP_FROZEN_SEED), chosen on the CPU
+# (tests/test_bp_ref.py) so that early_stop_inputs shows rows that stop after 1 iteration, after 2 ... 9 and never.
+# At n = 2 no message depends on an earlier iteration and every row of early_stop_inputs stops after the first.
+EARLY_STOP_SIZES = (2, 4, 8, 16, 32, 128, 256, 512)
+EARLY_STOP_FROZEN_SEED = 0
+EARLY_STOP_ITERS = 10
+PAST_GRID_ROWS = 64 * 1024 * 2 + 5  # n = 8: 64 codewords a work-group, 1024 work-groups at most
+
+
+def past_grid_early_stop_inputs():
+    """(frozen_pos, logits [PAST_GRID_ROWS, 8]): early_stop_inputs' 44 rows (noiseless, noisy, noise) tiled over
+    the batch with seeded row order, so every work-group of both strides holds rows of every class."""
+    fp = rate_half_frozen(8, EARLY_STOP_FROZEN_SEED)
+    base = early_stop_inputs(8, fp)
+    idx = np.random.default_rng(8).integers(0, len(base), PAST_GRID_ROWS)
+    return fp, base[idx]

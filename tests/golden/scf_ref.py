@@ -27,7 +27,10 @@ F32 = np.float32
 
 # 5G CRC polynomials (3GPP TS 38.212 5.1), exponents: the names polar_amd.mysn.crc_params takes
 CRC_POLYS = {"CRC24C": [24, 23, 21, 20, 17, 15, 13, 12, 8, 4, 2, 1, 0], "CRC16": [16, 12, 5, 0],
-             "CRC11": [11, 10, 9, 5, 0], "CRC6": [6, 5, 0]}
+             "CRC11": [11, 10, 9, 5, 0], "CRC6": [6, 5, 0],
+             # no 5G polynomials: x^3 + x + 1, x^2 + x + 1 and the parity check x + 1, for codes of fewer than 6
+             # information bits
+             "CRC3": [3, 1, 0], "CRC2": [2, 1, 0], "CRC1": [1, 0]}
 
 
 def crc_params(name):
@@ -60,10 +63,14 @@ def crc_ok(bits, deg, g):
     return crc_register(bits, deg, g) == 0
 
 
-def sc_flip(llr_logits, frozen_pos, n, flip, llr_max=30.0, exact=False):
+def sc_flip(llr_logits, frozen_pos, n, flip, llr_max=30.0, exact=False, false_r0=None, bl0=None):
     """Leaf-by-leaf SC of logits [rows, n] with the decision at flip[row] (-1: none) inverted.
     Returns (u [rows, n] uint8, alpha [rows, n] fp32 -- NaN at leaves of all-frozen nodes, which SC never
-    computes --, fragile [rows] bool)."""
+    computes --, fragile [rows] bool).
+    false_r0 / bl0 name one node (s, q), the stage-s node at position q << s, at which a deliberately WRONG
+    decoder is modelled (tests/test_tree_zoo_ref.py only): false_r0 treats the node as all frozen although it
+    is not; bl0 computes the node's g with the left child's partial sums taken as 0 although the left child was
+    decoded."""
     x = np.ascontiguousarray(llr_logits, dtype=F32)
     rows = x.shape[0]
     assert x.shape[1] == n and n >= 2 and n & (n - 1) == 0
@@ -78,7 +85,8 @@ def sc_flip(llr_logits, frozen_pos, n, flip, llr_max=30.0, exact=False):
 
     def node(a, llr):
         m = llr.shape[1]
-        if frozen[a:a + m].all():
+        here = (m.bit_length() - 1, a // m)
+        if frozen[a:a + m].all() or here == false_r0:
             return np.zeros((rows, m), dtype=np.uint8)
         if m == 1:
             alpha[:, a] = llr[:, 0]
@@ -96,7 +104,7 @@ def sc_flip(llr_logits, frozen_pos, n, flip, llr_max=30.0, exact=False):
             else:
                 f = genie_ref.f_minsum(lo, hi, llr_max)
             bl = node(a, f)
-        br = node(a + h, genie_ref.g_op(lo, hi, bl))
+        br = node(a + h, genie_ref.g_op(lo, hi, np.zeros_like(bl) if here == bl0 else bl))
         return np.concatenate([bl ^ br, br], axis=1)
 
     with np.errstate(over="ignore", invalid="ignore"):
@@ -112,9 +120,11 @@ def candidates(alpha, frozen_pos, n, t):
     return info[order[:, :t]]
 
 
-def scf_decode(llr_logits, frozen_pos, n, crc, max_flips, llr_max=30.0, exact=False):
+def scf_decode(llr_logits, frozen_pos, n, crc, max_flips, llr_max=30.0, exact=False, flip_tree=None):
     """crc: (degree, mask).  Returns a dict: bits [rows, k] uint8, crc_ok [rows] bool, flip_pos and attempts
-    [rows] int32, fragile [rows] bool, alpha [rows, n] fp32 (attempt 0), cand [rows, T'] (-1 rows that pass)."""
+    [rows] int32, fragile [rows] bool, alpha [rows, n] fp32 (attempt 0), cand [rows, T'] (-1 rows that pass).
+    flip_tree: sc_flip's false_r0 / bl0 switches, applied to the flip attempts alone (on the device attempt 0
+    and the candidates come from other kernels than the flip decodes)."""
     x = np.ascontiguousarray(llr_logits, dtype=F32)
     rows = x.shape[0]
     deg, g = crc
@@ -131,7 +141,8 @@ def scf_decode(llr_logits, frozen_pos, n, crc, max_flips, llr_max=30.0, exact=Fa
     if tp > 0 and len(fail):
         cand[fail] = c = candidates(alpha[fail], frozen_pos, n, tp)
         # every (failing row, attempt) pair as one batch
-        ut, _, fr = sc_flip(np.repeat(x[fail], tp, axis=0), frozen_pos, n, c.reshape(-1), llr_max, exact)
+        ut, _, fr = sc_flip(np.repeat(x[fail], tp, axis=0), frozen_pos, n, c.reshape(-1), llr_max, exact,
+                            **(flip_tree or {}))
         okt = crc_ok(ut[:, info], deg, g).reshape(len(fail), tp)
         fragile[fail] |= fr.reshape(len(fail), tp).any(axis=1)
         ut = ut[:, info].reshape(len(fail), tp, k)
@@ -230,3 +241,64 @@ def case_inputs(case):
     _, x = awgn_rows(seed, fp, n, crc, ROWS, ebno)
     x[-4:] = genie_ref.special_llrs(np.random.default_rng(seed + 1), 4, n)
     return fp, crc, x
+
+
+# ---- n = 2 and n = 4: every frozen pattern, every row of a small integer grid --------------------------
+# pl_plan_set_crc takes no CRC of a degree above k, so none of the pinned ones (CRC6 is the smallest) at
+# n <= 4: tests/test_scf_gpu.py checks that refusal and runs these lengths on the two small polynomials.
+TINY_GRID = {2: (-3, -2, -1, 0, 1, 2, 3), 4: (-2, -1, 0, 1, 2)}
+
+
+def tiny_cases(n):
+    """[(name, frozen_pos, CRC name, max_flips = k)]: every frozen pattern of n = 2 / 4 with k >= 1, on CRC1,
+    and on CRC3 as well where k >= 3."""
+    out = []
+    for pattern in range((1 << n) - 1):
+        fp = np.array([i for i in range(n) if (pattern >> i) & 1], dtype=np.int64)
+        k = n - len(fp)
+        for crc_name in ("CRC1", "CRC3"):
+            if k >= crc_params(crc_name)[0]:
+                out.append((f"n{n}_frozen{pattern:0{n}b}_{crc_name}", fp, crc_name, k))
+    return out
+
+
+def tiny_rows(n):
+    """Every row of TINY_GRID[n]^n, in lexicographic order: zeros and ties in (|alpha|, i) in most of them."""
+    import itertools
+    return np.array(list(itertools.product(TINY_GRID[n], repeat=n)), dtype=F32)
+
+
+# ---- the in-kernel CRC remainder table: k up to kScfMaxK = 1024, k just above a power of two -----------
+# (name, n, k, CRC, seed).  min-sum, max_flips = 4.  Position 0 is an information position (rank 0).
+CRC_TABLE_CASES = [
+    ("k1024_all_information", 1024, 1024, "CRC24C", 0),
+    ("k1000", 1024, 1000, "CRC16", 1),
+    ("k129", 1024, 129, "CRC11", 2),
+    ("k65", 1024, 65, "CRC6", 3),
+    ("k63_n64_no_doubling", 64, 63, "CRC11", 4),
+]
+CRC_TABLE_FLIPS = 4
+CRC_TABLE_ROWS = 16
+
+
+def crc_table_inputs(case):
+    """(frozen_pos, (degree, mask), logits [16, n], sent bits [8, k]).  The frozen set is seeded and leaves
+    position 0 free.  Rows 0 ... 7: a codeword with a valid CRC at +-8 whose channel position 0 is weakly wrong
+    (-1/16 of its value): every f that sees it passes its sign and magnitude 1/2 on and every g outweighs it, so
+    attempt 0 gets u_0 alone wrong, with the smallest |alpha|, and attempt 1 (a flip at position 0) must pass
+    the CRC over all k bits -- about half of them 1, u_0 = 1 in rows 0 ... 3.  Rows 8 ... 15: noise alone."""
+    name, n, k, crc_name, seed = case
+    rng = np.random.default_rng([77, seed])
+    fp = np.sort(1 + rng.permutation(n - 1)[: n - k]).astype(np.int64)
+    deg, g = crc_params(crc_name)
+    info = np.setdiff1d(np.arange(n), fp)
+    half = CRC_TABLE_ROWS // 2
+    msg = (rng.random((half, k - deg)) < 0.5).astype(np.uint8)
+    msg[:, 0] = np.arange(half) < half // 2
+    bits = crc_attach(msg, deg, g)
+    u = np.zeros((half, n), dtype=np.uint8)
+    u[:, info] = bits
+    x = ((2.0 * encode(u) - 1.0) * 8.0).astype(F32)
+    x[:, 0] = -x[:, 0] / F32(16.0)
+    noise = (rng.standard_normal((CRC_TABLE_ROWS - half, n)) * 4).astype(F32)
+    return fp, (deg, g), np.concatenate([x, noise]), bits

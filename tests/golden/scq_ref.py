@@ -44,27 +44,35 @@ def quantizer_vectors():
     return x.astype(np.float32), float(inv), 6, want.astype(np.int8)
 
 
-def _node(a, frozen, im, stats):
-    """a [rows, m] int32, frozen [m] bool -> the node's partial sums [rows, m] (uint8) and its u [rows, m]."""
+def _node(a, frozen, im, stats, pos=0, wrong=None):
+    """a [rows, m] int32, frozen [m] bool -> the node's partial sums [rows, m] (uint8) and its u [rows, m].
+    pos: the node's first position; wrong: sc_decode's false_r0 / bl0 switches."""
     m = a.shape[1]
+    here = (m.bit_length() - 1, pos // m)
+    if wrong and wrong.get("false_r0") == here:
+        return np.zeros(a.shape, np.uint8), np.zeros(a.shape, np.uint8)
     if m == 1:
         u = np.zeros(a.shape, np.uint8) if frozen[0] else (~(a > 0)).astype(np.uint8)
         return u, u
     h = m // 2
     x, y = a[:, :h], a[:, h:]
     fl = np.sign(x) * np.sign(y) * np.minimum(np.abs(x), np.abs(y))
-    bl, ul = _node(fl, frozen[:h], im, stats)
-    s = y + (1 - 2 * bl.astype(np.int32)) * x
+    bl, ul = _node(fl, frozen[:h], im, stats, pos, wrong)
+    bg = np.zeros_like(bl) if wrong and wrong.get("bl0") == here else bl
+    s = y + (1 - 2 * bg.astype(np.int32)) * x
     gr = np.clip(s, -im, im)
     stats["g_total"] += s.size
     stats["g_clamped"] += int((gr != s).sum())
-    br, ur = _node(gr, frozen[h:], im, stats)
+    br, ur = _node(gr, frozen[h:], im, stats, pos + h, wrong)
     return np.concatenate([bl ^ br, br], axis=1), np.concatenate([ul, ur], axis=1)
 
 
-def sc_decode(llr_q, frozen_pos, q_internal, return_stats=False):
+def sc_decode(llr_q, frozen_pos, q_internal, return_stats=False, wrong=None):
     """llr_q [rows, n] int8 (logit sign, any value) -> [rows, k] uint8 bits at the information positions,
-    ascending.  return_stats: also {"load_clamped", "g_clamped", "g_total"}, counts over the whole call."""
+    ascending.  return_stats: also {"load_clamped", "g_clamped", "g_total"}, counts over the whole call.
+    wrong = {"false_r0": (s, q)} or {"bl0": (s, q)} models a deliberately WRONG decoder at the stage-s node at
+    position q << s (tests/test_tree_zoo_ref.py only): the node is treated as all frozen although it is not, or
+    its g is computed with the left child's partial sums taken as 0 although the left child was decoded."""
     q = np.asarray(llr_q)
     assert q.dtype == np.int8 and q.ndim == 2
     n = q.shape[1]
@@ -75,7 +83,7 @@ def sc_decode(llr_q, frozen_pos, q_internal, return_stats=False):
     q32 = q.astype(np.int32)
     a = -np.clip(q32, -im, im)
     stats = {"load_clamped": int((np.abs(q32) > im).sum()), "g_clamped": 0, "g_total": 0}
-    _, u = _node(a, frozen, im, stats)
+    _, u = _node(a, frozen, im, stats, 0, wrong)
     bits = np.ascontiguousarray(u[:, ~frozen])
     return (bits, stats) if return_stats else bits
 

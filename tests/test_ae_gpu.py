@@ -73,6 +73,15 @@ def test_grid_cases_equal_the_restatement_exactly(case):
     _assert_exact(_run(_plan(case[1], fp), x, table), ref, case[0])
 
 
+def test_more_rows_than_the_grid():
+    """n = 8, M = 3, 4136 rows of grid logits on a 4096-block grid: the second stride reuses s_a and s_x."""
+    case, rows = ae_ref.PAST_GRID_CASE
+    fp, table, x = ae_ref.case_inputs(case, rows)
+    assert len(x) == rows > 4096
+    ref = ae_ref.ae_decode(x, fp, case[1], table)
+    _assert_exact(_run(_plan(case[1], fp), x, table), ref, case[0])
+
+
 @pytest.mark.parametrize("case", ae_ref.AWGN_CASES, ids=lambda c: c[0])
 def test_awgn_cases_within_the_rounding_of_the_metric(case):
     fp, table, x = ae_ref.case_inputs(case)
@@ -138,7 +147,7 @@ def _call(plan, x, table, m_tot=None, bs=None, kind=None, outs=(True, True), buf
 
 def test_abi_optional_outputs_output_kinds_and_argument_checks():
     from polar_amd import _lib, ops
-    case = ae_ref.GRID_CASES[3]  # n = 32
+    case = next(c for c in ae_ref.GRID_CASES if c[0] == "g32")  # n = 32
     fp, table, x = ae_ref.case_inputs(case)
     n = case[1]
     ref = ae_ref.ae_decode(x, fp, n, table)
@@ -179,7 +188,7 @@ def test_hip_graph_capture_and_replay():
     """One call captured into a HIP graph on a single stream and replayed once on inputs written into the same
     buffers afterwards: the replay equals the eager call."""
     from polar_amd import _lib, ops
-    case = ae_ref.GRID_CASES[6]  # n = 256, M = 33: two passes
+    case = next(c for c in ae_ref.GRID_CASES if c[0] == "g256_m33")  # n = 256, M = 33: two passes
     fp, table, x = ae_ref.case_inputs(case)
     n = case[1]
     plan = _plan(n, fp)
@@ -201,7 +210,7 @@ def test_hip_graph_capture_and_replay():
 
 def test_module():
     import polar_amd
-    case = ae_ref.GRID_CASES[3]  # n = 32, RM(2,5), M = 8
+    case = next(c for c in ae_ref.GRID_CASES if c[0] == "g32")  # n = 32, RM(2,5), M = 8
     fp, table, x = ae_ref.case_inputs(case)
     n = case[1]
     x = x[:15].reshape(3, 5, n)

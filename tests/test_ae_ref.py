@@ -74,6 +74,21 @@ def test_grid_cases_tie_and_are_exact_in_fp32(case):
             assert np.array_equal(acc.astype(np.float64), ref["metric"][t]), (case[0], t)
 
 
+def test_past_grid_case_winners_spread_over_both_strides():
+    """The 4136-row case: its table is valid, and rows past the grid's 4096 work-groups are won by every
+    candidate, with ties among them."""
+    case, rows = ae_ref.PAST_GRID_CASE
+    fp, table, x = ae_ref.case_inputs(case, rows)
+    n = case[1]
+    assert rows == 4099 + 37 and table.shape == (3, n)
+    assert all(automorphism.is_permutation(pi, n) for pi in table) and np.array_equal(table[0], np.arange(n))
+    ref = ae_ref.ae_decode(x, fp, n, table)
+    late = ref["best_idx"][4096:]
+    ties = (ref["metric"] == ref["metric"].min(axis=0)).sum(axis=0)
+    print("winners past the grid:", np.bincount(late, minlength=3), "tied rows there:", int((ties[4096:] >= 2).sum()))
+    assert set(late) == {0, 1, 2} and (ties[4096:-1] >= 2).any()
+
+
 def test_large_grid_cases_tie():
     for case in [c for c in ae_ref.GRID_CASES if c[1] > 256]:
         fp, table, x = ae_ref.case_inputs(case)
@@ -87,7 +102,7 @@ def test_large_grid_cases_tie():
 def test_candidates_are_codewords_and_identity_is_sc():
     """Every candidate of an automorphism table is a codeword (its frozen positions re-encode to 0), candidate 0
     (the identity) is plain SC, and the winner's metric is the distance of the re-encoded winner."""
-    case = ae_ref.AWGN_CASES[1]
+    case = next(c for c in ae_ref.AWGN_CASES if c[0] == "a128")
     fp, table, x = ae_ref.case_inputs(case)
     n = case[1]
     ref = ae_ref.ae_decode(x, fp, n, table)

@@ -97,6 +97,46 @@ def test_early_stop(n, exact):
     assert np.array_equal(off["iters"], np.full(len(x), 10, dtype=np.int32))
 
 
+@pytest.mark.parametrize("n", bp_ref.EARLY_STOP_SIZES)
+def test_early_stop_every_size(n):
+    """Min-sum early stop at the sizes of both stop paths that test_early_stop leaves out: n = 2 ... 32 (2 to 32
+    codewords in one wave) and n = 128, 256, 512.  Rows stop after 1 iteration, after a few and never; at n = 2 no
+    message depends on an earlier iteration and every row of these inputs stops after the first, so only that
+    class is asserted there."""
+    fp = bp_ref.rate_half_frozen(n, bp_ref.EARLY_STOP_FROZEN_SEED)
+    x = bp_ref.early_stop_inputs(n, fp)
+    ref = bp_ref.bp_decode(x, fp, n, bp_ref.EARLY_STOP_ITERS, 19.3, early_stop=True)
+    it = ref["iters"]
+    print(f"n={n}: iters {it.tolist()}")
+    assert (it == 1).any()
+    assert n == 2 or (((it > 1) & (it < 10)).any() and (it == 10).any())
+    _assert_equal(_run(_plan(n, fp), x, bp_ref.EARLY_STOP_ITERS, early_stop=True), ref, what=f"early stop n={n}")
+
+
+@pytest.mark.parametrize("n", [64, 256])
+def test_early_stop_scaled_minsum(n):
+    fp = bp_ref.rate_half_frozen(n, bp_ref.EARLY_STOP_FROZEN_SEED)
+    x = bp_ref.early_stop_inputs(n, fp)
+    ref = bp_ref.bp_decode(x, fp, n, 10, 19.3, scale=0.9375, early_stop=True)
+    it = ref["iters"]
+    print(f"n={n} scale=0.9375: iters {it.tolist()}")
+    assert (it == 1).any() and ((it > 1) & (it < 10)).any() and (it == 10).any()
+    assert not np.array_equal(it, bp_ref.bp_decode(x, fp, n, 10, 19.3, early_stop=True)["iters"])
+    _assert_equal(_run(_plan(n, fp), x, 10, scale=0.9375, early_stop=True), ref, what=f"early stop scaled n={n}")
+
+
+def test_early_stop_ragged_and_past_the_grid():
+    """n = 8, bs = 64 * 1024 * 2 + 5: every work-group starts a second stride with fresh `act` and `done`, and
+    the last one holds 5 valid codewords; noiseless, noisy and noise rows in every group."""
+    fp, x = bp_ref.past_grid_early_stop_inputs()
+    assert len(x) == 64 * 1024 * 2 + 5
+    ref = bp_ref.bp_decode(x, fp, 8, 6, 19.3, early_stop=True)
+    it = ref["iters"]
+    print("iters histogram:", np.bincount(it, minlength=7).tolist(), "last five:", it[-5:].tolist())
+    assert (it == 1).any() and ((it > 1) & (it < 6)).any() and (it == 6).any()
+    _assert_equal(_run(_plan(8, fp), x, 6, early_stop=True), ref, what="early stop past the grid")
+
+
 def test_batch_edges_and_optional_outputs():
     from polar_amd import ops
     n = 8

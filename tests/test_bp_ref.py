@@ -108,6 +108,31 @@ def test_early_stop_against_the_full_run(exact):
             assert np.array_equal(short[key][0], es[key][i])
 
 
+@pytest.mark.parametrize("n", bp_ref.EARLY_STOP_SIZES + (64,))
+def test_early_stop_gpu_inputs_show_every_class(n):
+    """The inputs of tests/test_bp_gpu.py's early-stop cases: rows that stop after 1 iteration, after 2 ... 9 and
+    never, plain and (n = 64, 256) scaled; at n = 2 only the first class exists."""
+    fp = bp_ref.rate_half_frozen(n, bp_ref.EARLY_STOP_FROZEN_SEED)
+    x = bp_ref.early_stop_inputs(n, fp)
+    for scale in (1.0, 0.9375) if n in (64, 256) else (1.0,):
+        if n == 64 and scale == 1.0:
+            continue
+        it = bp_ref.bp_decode(x, fp, n, bp_ref.EARLY_STOP_ITERS, 19.3, scale=scale, early_stop=True)["iters"]
+        print(f"n={n} scale={scale}: iters histogram {np.bincount(it, minlength=11).tolist()}")
+        assert (it == 1).any()
+        assert n == 2 or (((it > 1) & (it < 10)).any() and (it == 10).any())
+
+
+def test_past_grid_early_stop_inputs():
+    fp, x = bp_ref.past_grid_early_stop_inputs()
+    assert x.shape == (64 * 1024 * 2 + 5, 8)
+    it = bp_ref.bp_decode(x, fp, 8, 6, 19.3, early_stop=True)["iters"]
+    assert (it == 1).any() and ((it > 1) & (it < 6)).any() and (it == 6).any()
+    for g in (0, 1024, 2047):  # a work-group of the first stride, of the second, and the last full one
+        assert len(set(it[64 * g: 64 * g + 64])) >= 2
+    assert len(x) - 64 * 2048 == 5
+
+
 @pytest.mark.parametrize("n,num_iter,llr_max", EXACT_CASES)
 def test_fragile_rows_of_the_gpu_inputs_are_few(n, num_iter, llr_max):
     """A row at n = 1024 over 3 iterations evaluates about 6e4 f, each with five roundings and a 2^-27-ulp

@@ -16,6 +16,10 @@ import genie_ref  # noqa: E402
 import scf_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
+
+
+def _case(name):
+    return next(c for c in scf_ref.MINSUM_CASES if c[0] == name)
 DEV = "cuda:0"
 KEYS = ("bits", "crc_ok", "flip_pos", "attempts")
 
@@ -68,6 +72,41 @@ def test_exact_f_equals_the_restatement(case):
     _assert_equal(_run(_plan(n, fp, crc, 1, lmax), x, T), ref, keep=~ref["fragile"], what=case[0])
 
 
+@pytest.mark.parametrize("n", [2, 4])
+def test_n2_and_n4_every_frozen_pattern(n):
+    """The two shortest lengths of the flip kernel (n = 2 is its bottom-only root).  pl_plan_set_crc takes no
+    degree above k, so the smallest pinned CRC (CRC6) is refused for every pattern: that is checked by return
+    code and message, and the patterns run on x + 1 and, from k = 3, x^3 + x + 1, with T = k, on every row of a
+    small integer grid (zeros and ties in (|alpha|, i) in most rows)."""
+    import polar_amd
+    from polar_amd import _lib
+    x = scf_ref.tiny_rows(n)
+    cases = scf_ref.tiny_cases(n)
+    assert len(cases) >= (1 << n) - 1
+    for name, fp, crc_name, T in cases:
+        plan = _plan(n, fp, None)
+        rc = _lib.lib().pl_plan_set_crc(plan.handle, *scf_ref.crc_params("CRC6"))
+        assert rc == _lib.PL_EINVAL and b"pl_plan_set_crc" in _lib.lib().pl_last_error_string(), name
+        crc = scf_ref.crc_params(crc_name)
+        ref = scf_ref.scf_decode(x, fp, n, crc, T)
+        assert (ref["attempts"] > 1).any() and (ref["flip_pos"] >= 0).any(), name
+        _assert_equal(_run(_plan(n, fp, crc), x, T), ref, what=name)
+
+
+@pytest.mark.parametrize("case", scf_ref.CRC_TABLE_CASES, ids=[c[0] for c in scf_ref.CRC_TABLE_CASES])
+def test_in_kernel_crc_table(case):
+    """k = 1024 (the maximum), k just above a power of two, and k = 63 where the doubling loop must not run: 8
+    rows whose only wrong decision is u_0 (rank 0, the one reader of the table's last entry; u_0 = 1 in four of
+    them) and which the first flip must rescue through a CRC over all k bits, and 8 rows of noise."""
+    fp, crc, x, sent = scf_ref.crc_table_inputs(case)
+    n, T = case[1], scf_ref.CRC_TABLE_FLIPS
+    ref = scf_ref.scf_decode(x, fp, n, crc, T)
+    won = ref["flip_pos"] >= 0
+    assert (ref["attempts"] > 1).all() and won[:8].all() and np.array_equal(ref["bits"][:8], sent)
+    assert (ref["bits"][won, 0] == 1).any() and (ref["bits"][won, 0] == 0).any() and (~ref["crc_ok"]).any()
+    _assert_equal(_run(_plan(n, fp, crc), x, T), ref, what=case[0])
+
+
 def test_awkward_llrs():
     """Rows of zeros, -0, integer ties and a saturated row only: the (|alpha|, i) order and HD(+-0)."""
     for n, spec, crc_name, T in ((16, "half:16", "CRC6", 8), (64, "ref", "CRC11", 16), (256, "ref", "CRC24C", 64)):
@@ -80,7 +119,7 @@ def test_awkward_llrs():
 
 def test_max_flips_0_is_sc_plus_crc_status_and_first_pass_rows_are_sc_rows():
     from polar_amd import _lib, ops
-    case = scf_ref.MINSUM_CASES[2]  # n = 32, the reference set: its specialised min-sum kernel is pre-built
+    case = _case("n32")  # n = 32, the reference set: its specialised min-sum kernel is pre-built
     fp, crc, x = scf_ref.case_inputs(case)
     xt = torch.as_tensor(x, device=DEV)
     for flags in (_lib.PL_PLAN_GENERIC, _lib.PL_PLAN_CACHE_ONLY):
@@ -180,7 +219,7 @@ def _call(plan, x, max_flips, bs=None, kind=None, outs=(True, True, True), bufs=
 
 def test_optional_outputs_output_kinds_and_out_reuse():
     from polar_amd import _lib, ops
-    case = scf_ref.MINSUM_CASES[4]  # n = 64
+    case = _case("n64")  # n = 64
     fp, crc, x = scf_ref.case_inputs(case)
     n, T = 64, case[4]
     ref = scf_ref.scf_decode(x, fp, n, crc, T)
@@ -234,7 +273,7 @@ def test_hip_graph_capture_and_replay():
     synchronisation inside it would fail the capture) and replayed on inputs written into the same buffers
     afterwards: the failing rows and their number are new, and the replay equals the eager call."""
     from polar_amd import _lib, ops
-    case = scf_ref.MINSUM_CASES[6]  # n = 256, T = 16
+    case = _case("n256")  # n = 256, T = 16
     fp, crc, x = scf_ref.case_inputs(case)
     n, T = case[1], case[4]
     plan = _plan(n, fp, crc)
@@ -261,7 +300,7 @@ def test_module():
     import polar_amd
     n = 64
     fp = polar_amd.reference_frozen_pos(32, n)
-    case = scf_ref.MINSUM_CASES[4]
+    case = _case("n64")
     _, crc, x = scf_ref.case_inputs(case)
     x = x[:60].reshape(3, 20, n)
     ref = scf_ref.scf_decode(x.reshape(-1, n), fp.numpy(), n, crc, 16)

@@ -156,6 +156,43 @@ def test_crc_register_against_polynomial_division():
         assert not scf_ref.crc_ok(cw, deg, g).any()
 
 
+@pytest.mark.parametrize("n", [2, 4])
+def test_tiny_cases_against_the_naive_decoder(n):
+    """Every frozen pattern of n = 2 and n = 4 with k >= 1 is there; on every grid row the restatement equals the
+    naive per-row decoder; rows fail, rows are rescued, candidates tie, and CRC3 leaves rows no flip rescues."""
+    x = scf_ref.tiny_rows(n)
+    cases = scf_ref.tiny_cases(n)
+    assert {tuple(c[1]) for c in cases} == {tuple(i for i in range(n) if (p >> i) & 1) for p in range((1 << n) - 1)}
+    tied = never = 0
+    for name, fp, crc_name, T in cases:
+        crc = scf_ref.crc_params(crc_name)
+        assert T == n - len(fp) >= crc[0]
+        r = scf_ref.scf_decode(x, fp, n, crc, T)
+        want = _naive_scf(x, fp, n, crc, T)
+        assert np.array_equal(r["bits"], np.array([w[0] for w in want], dtype=np.uint8)), name
+        assert np.array_equal(r["flip_pos"], np.array([w[2] for w in want])), name
+        assert np.array_equal(r["attempts"], np.array([w[3] for w in want])), name
+        assert (r["attempts"] > 1).any() and (r["flip_pos"] >= 0).any(), name
+        tied += T > 1 and _has_tie(r)
+        never += int((~r["crc_ok"]).sum())
+    print(f"n={n}: {len(cases)} cases, {tied} with tied candidates, {never} rows never rescued")
+    assert (tied > 0 and never > 0) or n == 2  # n = 2: CRC1 alone, and no failing row of the k = 2 code ties
+
+
+@pytest.mark.parametrize("case", scf_ref.CRC_TABLE_CASES, ids=[c[0] for c in scf_ref.CRC_TABLE_CASES])
+def test_crc_table_inputs(case):
+    """Every row fails attempt 0; rows 0 ... 7 are rescued by the flip at position 0 (information rank 0) and
+    decode to the sent bits, u_0 = 1 in some; the noise rows are never rescued."""
+    fp, crc, x, sent = scf_ref.crc_table_inputs(case)
+    name, n, k = case[:3]
+    assert n - len(fp) == k <= 1024 and 0 not in fp and len(x) <= 16
+    r = scf_ref.scf_decode(x, fp, n, crc, scf_ref.CRC_TABLE_FLIPS)
+    assert (r["attempts"] > 1).all()
+    assert (r["flip_pos"][:8] == 0).all() and (r["attempts"][:8] == 2).all() and np.array_equal(r["bits"][:8], sent)
+    assert (sent[:4, 0] == 1).all() and (sent[4:, 0] == 0).all()
+    assert not r["crc_ok"][8:].any() and not r["fragile"].any()
+
+
 def _classes(r):
     first = int(r["crc_ok"].sum() - (r["flip_pos"] >= 0).sum())
     return first, int((r["flip_pos"] >= 0).sum()), int((~r["crc_ok"]).sum())
