@@ -331,7 +331,9 @@ class Plan:
         return self._h
 
     def set_crc(self, degree, poly_mask):
-        """CRC-aided path selection for SCL plans (pl_plan_set_crc)."""
+        """CRC-aided path selection for SCL plans (pl_plan_set_crc): 0 <= degree <= min(31, k), 0 turns it
+        off, poly_mask without bits at or above x^degree.  Anything else raises (PL_EINVAL) and the plan
+        keeps the CRC it had."""
         check(lib().pl_plan_set_crc(self._h, int(degree), int(poly_mask)), "pl_plan_set_crc")
 
     def kernel(self):
