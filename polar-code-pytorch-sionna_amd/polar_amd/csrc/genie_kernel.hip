@@ -7,7 +7,7 @@
 // So the n leaves are a log2 n-stage butterfly of (f, g) pairs over a = -logits, top stage first,
 //     x = a[p], y = a[p + h], a[p] = f(x, y), a[p + h] = g(x, y, beta_{s-1}[p]),  h = 2^(s-1),
 // for every p whose index bit s - 1 is 0, with no serial dependency inside a stage and no
-// data-dependent control flow.  f and g are sc_kernel.hip's fop / gop, restated here.
+// data-dependent control flow.  f and g are the SC decoder's fop / gop (sc_tree.h).
 //
 // Layout: a codeword is held by G = max(1, n / 32) lanes, element p in lane p % G, slot p / G, E =
 // min(n, 32) slots a lane; a wave holds C = 64 / G codewords.  Stages with h >= G pair two slots of
@@ -30,6 +30,7 @@
 #include "../../../include/polar_mi355x.h"
 #include "exactf.h"
 #include "plan.h"
+#include "sc_tree.h"
 
 namespace {
 
@@ -37,20 +38,8 @@ constexpr int kWaves = 4;        // waves per block
 constexpr int kMinWaves = 2;     // waves per SIMD the register allocation must allow: at 3 or 4 the n >= 64 kernels spill
 constexpr int kMaxBlocks = 1024;  // grid cap: 256 CUs x 2 waves per SIMD x 4 SIMDs / 4 waves a block, twice over
 
-template <int FM>
-__device__ __forceinline__ float fop(float x, float y, float lmax) {
-    if constexpr (FM == 0) {  // sc_kernel.hip fop<0> (polar_sc.py:46)
-        const float m = fminf(fminf(fabsf(x), fabsf(y)), lmax);
-        const uint32_t sg = (__float_as_uint(x) ^ __float_as_uint(y)) & 0x80000000u;
-        return __uint_as_float(__float_as_uint(m) | sg);
-    } else {
-        return plx::f_exact(x, y, lmax);
-    }
-}
-// sc_kernel.hip gop (polar_sc.py:49-53): (u ? -x : x) + y, one rounding
-__device__ __forceinline__ float gop(float x, float y, uint32_t bit) {
-    return __uint_as_float(__float_as_uint(x) ^ (bit << 31)) + y;
-}
+using pl::tree::fop;
+using pl::tree::gop;
 
 // the value of lane ^ H
 template <int H>

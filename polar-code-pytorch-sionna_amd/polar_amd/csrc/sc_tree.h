@@ -1,5 +1,7 @@
 // sc_tree.h -- the register-tree SC decode of one lane group, shared by scf_kernel.hip (one inverted
 // decision per group) and ae_kernel.hip (one position permutation per group).  gfx950, wave64.
+// genie_kernel.hip takes fop / gop from here.  sc_kernel.hip and scq_kernel.hip still carry their own copies
+// of this walk.
 //
 // sc_kernel.hip's register tree -- G = max(1, n/128) lanes per decode, element i in lane i mod G, slot
 // i / G, the two top stages recomputed from the root LLRs -- without the repetition and SPC shortcuts
@@ -46,7 +48,7 @@ __device__ __forceinline__ uint32_t rl(uint32_t v, int idx) {
 
 template <int FM>
 __device__ __forceinline__ float fop(float x, float y, float lmax) {
-    if constexpr (FM == 0) {  // sc_kernel.hip fop<0> (polar_sc.py:46)
+    if constexpr (FM == 0) {  // min-sum, clipped at lmax (polar_sc.py:46)
         const float m = fminf(fminf(fabsf(x), fabsf(y)), lmax);
         const uint32_t sg = (__float_as_uint(x) ^ __float_as_uint(y)) & 0x80000000u;
         return __uint_as_float(__float_as_uint(m) | sg);
@@ -54,7 +56,8 @@ __device__ __forceinline__ float fop(float x, float y, float lmax) {
         return plx::f_exact(x, y, lmax);
     }
 }
-// sc_kernel.hip gop (polar_sc.py:49-53): (u ? -x : x) + y, one rounding
+// g (polar_sc.py:49-53): (u ? -x : x) + y, one rounding.  fop / gop are also genie_kernel.hip's; sc_kernel.hip
+// holds the same pair of its own
 __device__ __forceinline__ float gop(float x, float y, uint32_t bit) {
     return __uint_as_float(__float_as_uint(x) ^ (bit << 31)) + y;
 }
