@@ -9,6 +9,12 @@
  * No exceptions cross this boundary: 0 = success, negative = error, details from
  * pl_last_error_string() (thread-local).
  *
+ * Alignment: every float, int32_t and double pointer needs only the natural alignment of its
+ * element type (4, 4 and 8 bytes; a workspace holds fp64 tables and needs 8), and a uint8 output may
+ * start at any address: a contiguous [bs, n] view that begins anywhere inside a larger buffer is a
+ * valid argument.  A 16-byte aligned pointer only lets a kernel take its 16-byte load and store paths
+ * (faster, same values).  The one exception is pl_scq_decode's llr_q, as stated there.
+ *
  * Plans are device-bound: pl_plan_create allocates the plan's tables and loads its kernel module
  * on the device current at that call (hipSetDevice).  Decode/encode calls must pass a stream of
  * that device (or NULL with that device current); any other device gives PL_EINVAL.  Create one

@@ -77,13 +77,19 @@ def scl_decode(plan, llr_logits, out=None, out_dtype=torch.float32, return_pm=Fa
     bs = x.shape[0]
     if out is None:
         out = torch.empty((bs, plan.k), dtype=out_dtype, device=x.device)
+    elif out.shape != (bs, plan.k) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
     kind = _out_kind(out.dtype)
-    pm = torch.empty((bs, 2 * plan.list_size), dtype=torch.float64, device=x.device) if return_pm else None
     L = _lib.lib()
     ws_bytes = int(L.pl_scl_workspace_size(plan.handle, bs))
     ws = workspace if workspace is not None else scl_workspace(plan, bs, x.device)
-    if ws.device != x.device or ws.numel() < ws_bytes:
-        raise ValueError(f"workspace must hold {ws_bytes} bytes on {x.device}")
+    # the kernel lays fp64 tables over the workspace's first ws_bytes bytes: a wider dtype, a strided
+    # view or an address off 8 bytes would reach it as a raw pointer all the same
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous() \
+            or ws.device != x.device or ws.numel() < ws_bytes or (ws_bytes and ws.data_ptr() % 8):
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of at least {ws_bytes} elements on {x.device}, "
+                         "8-byte aligned (scl_workspace)")
+    pm = torch.empty((bs, 2 * plan.list_size), dtype=torch.float64, device=x.device) if return_pm else None
     with torch.cuda.device(x.device):
         st = _lib.current_stream_ptr(x.device)
         _lib.check(L.pl_scl_decode(plan.handle, ctypes.c_void_p(x.data_ptr()), bs, ctypes.c_void_p(out.data_ptr()),
@@ -369,6 +375,9 @@ def polar_encode(plan, u_bits, out=None):
     bs = u.shape[0]
     if out is None:
         out = torch.empty((bs, plan.n), dtype=torch.float32, device=u.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != (bs, plan.n) \
+            or not out.is_contiguous() or out.device != u.device:
+        raise ValueError("out must be a contiguous float32 [bs, n] tensor on the input's device")
     with torch.cuda.device(u.device):
         st = _lib.current_stream_ptr(u.device)
         _lib.check(_lib.lib().pl_polar_encode(plan.handle, ctypes.c_void_p(u.data_ptr()), bs,
@@ -685,7 +694,8 @@ def sc_decode_count(plan, llr_logits, ref_bits, counts=None):
         raise ValueError(f"llr_logits must be [bs, {plan.n}], got {tuple(x.shape)}")
     bs = x.shape[0]
     nq = (plan.k + 31) // 32
-    if ref_bits.shape != (bs, nq) or ref_bits.dtype != torch.int32 or ref_bits.device != x.device:
+    if not isinstance(ref_bits, torch.Tensor) or ref_bits.shape != (bs, nq) or ref_bits.dtype != torch.int32 \
+            or ref_bits.device != x.device:
         raise ValueError(f"ref_bits must be int32 [{bs}, {nq}] on the input's device")
     ref = ref_bits.contiguous()
     counts = _counts(counts, x.device)
