@@ -43,6 +43,8 @@
  *   pl_osd_decode    OSDecoder.forward  my_sn/fec/osd/dec.py:148-192 (_find_mrb :107-147, _find_min_dist :82-106)
  *   pl_bp_decode     the "iterative BP decoding" of my_sn/fec/polar/dec.py:1 and Polar5GDecoder's
  *                    dec_type "BP" (named there, not implemented)
+ *   pl_scan_decode   no reference counterpart (soft-cancellation decoding with soft output; the contract is
+ *                    stated below)
  *   pl_scf_decode    no reference counterpart (CRC-aided SC-Flip; the contract is stated below)
  *   pl_llr_quantize / pl_scq_decode: no reference counterpart (fixed-point SC on int8 LLRs; the contract
  *                    is stated below)
@@ -411,6 +413,45 @@ int pl_genie_count(int32_t n, int32_t f_mode, float llr_max, const float* llr_lo
 int pl_bp_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, int32_t num_iter, float scale,
                  uint32_t flags, void* out_bits, int32_t out_kind, float* soft_u, float* ext_x, int32_t* iters,
                  void* hip_stream);
+
+/* Soft-cancellation (SCAN) decoding with soft output (Fayyaz and Barry 2014; polar_amd.SCAN_Dec;
+ * csrc/scan_kernel.hip).  The reference has no such decoder.  pl_bp_decode's factor graph, unit equations and
+ * outputs on the schedule of the SC tree walk: decided and frozen leaves reach the rest of the tree within one
+ * iteration, so 1 .. 4 iterations do what flooding BP needs tens for.
+ * plan: a list-size-1 plan; its n (2 <= n <= 2048), frozen set, f_mode and llr_max (lmax below) are used.
+ * llr_logits [bs, n] fp32 logits log P(1)/P(0); inside, an LLR is a = -logit (positive favours 0).
+ * Messages L[s][i] (towards u) and R[s][i] (towards the channel), s = 0 .. S = log2 n.  L[S][i] =
+ * clip(-logit[i]); R[0][i] = +lmax at frozen positions, 0 at information positions; every other message starts
+ * at 0.  clip(v) = med3(v, -lmax, lmax).
+ * f: PL_F_MINSUM: magnitude min(|x|, |y|, lmax) -- times scale, rounded to fp32 once, when scale < 1 --
+ * with the xor of the two sign bits; PL_F_EXACT: pl_sc_decode's exact f (inputs clipped inside, the
+ * full-range form when lmax > 43).
+ * One iteration is node(S, 0).  node(0, .) does nothing.  node(s, b), s >= 1, h = 2^(s-1), for every i in
+ * [b, b+h):
+ *     L[s-1][i]   = clip(f(L[s][i], L[s][i+h] + R[s-1][i+h]))    R[s-1][i+h]: the previous iteration's value
+ *     node(s-1, b)                                               (0 in the first)
+ *     L[s-1][i+h] = clip(f(L[s][i], R[s-1][i]) + L[s][i+h])      R[s-1][i]: just written by the left child
+ *     node(s-1, b+h)
+ *     R[s][i]     = clip(f(R[s-1][i], L[s][i+h] + R[s-1][i+h]))
+ *     R[s][i+h]   = clip(f(R[s-1][i], L[s][i]) + R[s-1][i+h])
+ * every + one fp32 rounding, the inner sum not clipped before f.  These are pl_bp_decode's units.  Within a
+ * node each message is written once: the values do not depend on how the i are spread over lanes.
+ * Outputs after the last iteration run (any may be NULL, not all):
+ *   out_bits [bs, k], PL_OUT_F32 / PL_OUT_U8: !(L[0][i] > 0) at the information positions, ascending;
+ *   soft_u [bs, k] fp32: -L[0][i] there, logits log P(1)/P(0) like the input;
+ *   ext_x [bs, n] fp32: -R[S][i], the extrinsic logits of the code bits;
+ *   iters [bs] int32: the iterations the row ran.
+ * flags: 0 or PL_SCAN_EARLY_STOP: after each iteration, u^ = the hard decisions over all n positions (frozen
+ * ones 0) and x^[i] = !(L[S][i] + R[S][i] > 0); a row whose u^ encodes to x^ stops and keeps the messages
+ * of that iteration.  Without the flag, and for a row that never stops, iters is num_iter.
+ * No allocation, no workspace and no host synchronisation: the call can be captured into a HIP graph.  Natural
+ * alignment only.  bs == 0 is PL_OK.  PL_EINVAL (the message names the argument): num_iter < 1, scale outside
+ * (0, 1], scale != 1 with PL_F_EXACT, a list plan, all four outputs NULL, negative bs, a stream of another
+ * device.  NaN and Inf inputs are not supported. */
+#define PL_SCAN_EARLY_STOP 1u
+int pl_scan_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, int32_t num_iter, float scale,
+                   uint32_t flags, void* out_bits, int32_t out_kind, float* soft_u, float* ext_x, int32_t* iters,
+                   void* hip_stream);
 
 /* CRC-aided successive-cancellation flip decoding (SC-Flip; Afisiadis, Balatsoukas-Stimming, Burg 2014;
  * polar_amd.SCF_Dec; csrc/scf_kernel.hip).  The reference has no such decoder.  SC first; a row whose SC

@@ -28,6 +28,8 @@ class BP_Dec(nn.Module):
     After forward(): last_iters holds the iterations each row ran (int32, [...]), and with
     return_ext, last_ext the extrinsic logits of the code bits ([..., n]), on the input's device.
     """
+    # what SCAN_Dec (scan.py), the same module on another schedule, replaces
+    _NAME, _MAX_N, _decode = "BP", BP_MAX_N, staticmethod(ops.bp_decode)
 
     def __init__(self, frozen_pos, n, num_iter=20, hard_out=True, output_dtype=tc.float32, device='cpu', f='exact',
                  scale=1.0, early_stop=False, llr_max=19.3, return_ext=False):
@@ -35,8 +37,8 @@ class BP_Dec(nn.Module):
         n = int(n)
         if n < 2 or n & (n - 1):
             raise ValueError(f"n must be a power of 2, got {n}")
-        if n > BP_MAX_N:
-            raise ValueError(f"BP decoding of n = {n} is not supported by the MI355X kernel (n <= {BP_MAX_N})")
+        if n > self._MAX_N:
+            raise ValueError(f"{self._NAME} decoding of n = {n} is not supported by the MI355X kernel (n <= {self._MAX_N})")
         if f not in ("exact", "minsum"):
             raise ValueError(f"f must be 'exact' or 'minsum', got {f!r}")
         if int(num_iter) < 1:
@@ -77,8 +79,8 @@ class BP_Dec(nn.Module):
         lead = list(inputs.shape[:-1])
         llr = inputs.reshape([-1, self.n])
         dev = _gpu_for(llr, self.device)
-        res = ops.bp_decode(self.plan(dev), llr.to(dev, non_blocking=True), self.num_iter, self.scale, self.early_stop,
-                            hard=self.hard_out, soft=not self.hard_out, ext=self.return_ext, iters=True)
+        res = self._decode(self.plan(dev), llr.to(dev, non_blocking=True), self.num_iter, self.scale, self.early_stop,
+                           hard=self.hard_out, soft=not self.hard_out, ext=self.return_ext, iters=True)
         self.last_iters = res["iters"].reshape(lead).to(inputs.device)
         self.last_ext = res["ext_x"].reshape(lead + [self.n]).to(inputs.device) if self.return_ext else None
         out = res["bits"] if self.hard_out else res["soft_u"]

@@ -21,6 +21,8 @@ estimate of the maximum-likelihood curve: its BLER is comparable with SC / SCL (
 BER counts codeword bits.
 'bp' in --algos adds the belief-propagation decoder (BP_Dec, pl_bp_decode): --bp_iter iterations of --bp_f
 (exact or minsum, the latter scaled by --bp_scale), --bp_early_stop ends a row once its decisions re-encode.
+'scan' in --algos adds the soft-cancellation decoder (SCAN_Dec, pl_scan_decode): --scan_iter iterations (default 2)
+of --scan_f (exact or minsum); --code plain, n <= 2048.
 'scf' in --algos adds the CRC-aided SC-Flip decoder (SCF_Dec, pl_scf_decode) with --scf_flips candidate
 positions a row and the f of --scf_f; it needs --code 5g, the only code here with a CRC.
 'ae' in --algos adds the automorphism-ensemble SC decoder (AE_Dec, pl_ae_decode): --ae_perms permuted SC
@@ -84,6 +86,8 @@ def parse(argv=None):
     ap.add_argument("--bp_scale", type=float, default=1.0, help="BP leg, --bp_f minsum: the magnitude scale in (0, 1]")
     ap.add_argument("--bp_early_stop", action="store_true",
                     help="BP leg: a row stops once its hard decisions re-encode to those on the code bits")
+    ap.add_argument("--scan_iter", type=int, default=2, help="iterations of the SCAN leg ('scan' in --algos)")
+    ap.add_argument("--scan_f", choices=["exact", "minsum"], default="exact", help="f of the SCAN leg")
     ap.add_argument("--scf_flips", type=int, default=16,
                     help="SC-Flip leg ('scf' in --algos): candidate positions a row, 0 ... 64")
     ap.add_argument("--scf_f", choices=["exact", "minsum"], default="exact", help="f of the SC-Flip leg")
@@ -130,6 +134,14 @@ def parse(argv=None):
             ap.error("--bp_iter must be >= 1")
         if not 0.0 < c.bp_scale <= 1.0 or (c.bp_f == "exact" and c.bp_scale != 1.0):
             ap.error("--bp_scale must be in (0, 1], and 1 with --bp_f exact")
+    if "scan" in c.algos:
+        from .scan import SCAN_MAX_N
+        if c.code != "plain":
+            ap.error("'scan' in --algos needs --code plain")
+        if c.n > SCAN_MAX_N:
+            ap.error(f"'scan' in --algos needs --n <= {SCAN_MAX_N}")
+        if c.scan_iter < 1:
+            ap.error("--scan_iter must be >= 1")
     if "osd" in c.algos:
         from .osd import check_supported
         if c.code != "plain":
@@ -228,6 +240,9 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
         from .bp import BP_Dec
         dec = BP_Dec(fp, c.n, num_iter=c.bp_iter, device=dev_str, f=c.bp_f, scale=c.bp_scale,
                      early_stop=c.bp_early_stop)
+    elif mode == "scan":
+        from .scan import SCAN_Dec
+        dec = SCAN_Dec(fp, c.n, num_iter=c.scan_iter, device=dev_str, f=c.scan_f)
     elif mode == "ae":
         from .ae import AE_Dec
         try:  # the frozen set is known only here (--frozen design makes it on the GPU)
@@ -280,6 +295,8 @@ def main(argv=None):
         codes.append(gen_code(c, f"OSD-{c.osd_t} (codeword BER)", "osd", device, gen))
     if "bp" in c.algos:
         codes.append(gen_code(c, f"BP-{c.bp_iter} ({c.bp_f})", "bp", device, gen))
+    if "scan" in c.algos:
+        codes.append(gen_code(c, f"SCAN-{c.scan_iter} ({c.scan_f})", "scan", device, gen))
     if "scf" in c.algos:
         codes.append(gen_code(c, f"SCF-{c.scf_flips} ({c.scf_f})", "scf", device, gen))
     if "ae" in c.algos:

@@ -54,6 +54,9 @@ int launch_encode(const pl_plan* plan, const float* u, int64_t bs, float* cw, hi
 // belief propagation (bp_kernel.hip); pl_bp_decode has checked the arguments
 int launch_bp(const pl_plan* plan, const float* llr, int64_t bs, int num_iter, float scale, int early_stop,
               void* out_bits, int out_kind, float* soft_u, float* ext_x, int32_t* iters, hipStream_t stream);
+// soft cancellation (scan_kernel.hip); pl_scan_decode has checked the arguments
+int launch_scan(const pl_plan* plan, const float* llr, int64_t bs, int num_iter, float scale, int early_stop,
+                void* out_bits, int out_kind, float* soft_u, float* ext_x, int32_t* iters, hipStream_t stream);
 // fixed-point SC on int8 LLRs and the LLR quantiser (scq_kernel.hip); the callers have checked the arguments
 int launch_scq(const pl_plan* plan, const int8_t* llr_q, int64_t bs, int q_internal, void* out, int out_kind,
                hipStream_t stream);

@@ -630,14 +630,9 @@ def genie_count(n, llr_logits, u_bits, f_mode=0, llr_max=30.0, counts=None, retu
     return (counts, leaf) if return_leaf else counts
 
 
-def bp_decode(plan, llr_logits, num_iter=20, scale=1.0, early_stop=False, out_dtype=torch.float32, hard=True,
-              soft=False, ext=False, iters=False):
-    """pl_bp_decode: belief-propagation decode of [bs, n] fp32 logits with the list-size-1 `plan`
-    (its n <= 1024, frozen set, f mode and llr_max).  Returns a dict with the requested outputs:
-    'bits' [bs, k] (hard), 'soft_u' [bs, k] fp32 logits of the information bits (soft), 'ext_x' [bs, n]
-    fp32 extrinsic logits of the code bits (ext), 'iters' [bs] int32 iterations run (iters).  scale in
-    (0, 1] multiplies the min-sum magnitude; early_stop ends a row once its hard decisions re-encode
-    to the hard decisions on the code bits.  Nothing is synchronised: the call can be graph-captured."""
+def _soft_decode(entry, what, flag, plan, llr_logits, num_iter, scale, early_stop, out_dtype, hard, soft, ext, iters):
+    """The tensor side shared by bp_decode and scan_decode (one C signature): checks, the requested outputs,
+    the call of `entry` (a name in the library) on the input's device and current stream."""
     _require_cuda(llr_logits, "llr_logits")
     x = llr_logits
     if x.dtype != torch.float32 or not x.is_contiguous():
@@ -656,18 +651,38 @@ def bp_decode(plan, llr_logits, num_iter=20, scale=1.0, early_stop=False, out_dt
         out["iters"] = torch.empty((bs,), dtype=torch.int32, device=x.device)
     kind = _out_kind(out_dtype) if hard else _lib.PL_OUT_F32
     if not out:
-        raise ValueError("bp_decode: no output requested (hard, soft, ext, iters)")
+        raise ValueError(f"{what}: no output requested (hard, soft, ext, iters)")
     if bs == 0:  # empty tensors have no address to hand over
         return out
 
     def ptr(name):
         return ctypes.c_void_p(out[name].data_ptr() if name in out else 0)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().pl_bp_decode(plan.handle, ctypes.c_void_p(x.data_ptr()), bs, int(num_iter), float(scale),
-                                           _lib.PL_BP_EARLY_STOP if early_stop else 0, ptr("bits"), kind,
-                                           ptr("soft_u"), ptr("ext_x"), ptr("iters"),
-                                           _lib.current_stream_ptr(x.device)), "pl_bp_decode")
+        _lib.check(getattr(_lib.lib(), entry)(plan.handle, ctypes.c_void_p(x.data_ptr()), bs, int(num_iter), float(scale),
+                                              flag if early_stop else 0, ptr("bits"), kind, ptr("soft_u"), ptr("ext_x"),
+                                              ptr("iters"), _lib.current_stream_ptr(x.device)), entry)
     return out
+
+
+def bp_decode(plan, llr_logits, num_iter=20, scale=1.0, early_stop=False, out_dtype=torch.float32, hard=True,
+              soft=False, ext=False, iters=False):
+    """pl_bp_decode: belief-propagation decode of [bs, n] fp32 logits with the list-size-1 `plan`
+    (its n <= 1024, frozen set, f mode and llr_max).  Returns a dict with the requested outputs:
+    'bits' [bs, k] (hard), 'soft_u' [bs, k] fp32 logits of the information bits (soft), 'ext_x' [bs, n]
+    fp32 extrinsic logits of the code bits (ext), 'iters' [bs] int32 iterations run (iters).  scale in
+    (0, 1] multiplies the min-sum magnitude; early_stop ends a row once its hard decisions re-encode
+    to the hard decisions on the code bits.  Nothing is synchronised: the call can be graph-captured."""
+    return _soft_decode("pl_bp_decode", "bp_decode", _lib.PL_BP_EARLY_STOP, plan, llr_logits, num_iter, scale,
+                        early_stop, out_dtype, hard, soft, ext, iters)
+
+
+def scan_decode(plan, llr_logits, num_iter=2, scale=1.0, early_stop=False, out_dtype=torch.float32, hard=True,
+                soft=False, ext=False, iters=False):
+    """pl_scan_decode: soft-cancellation (SCAN) decode of [bs, n] fp32 logits with the list-size-1 `plan`
+    (its n <= 2048, frozen set, f mode and llr_max): bp_decode's messages, arguments and outputs on the
+    schedule of the SC tree walk.  Nothing is synchronised: the call can be graph-captured."""
+    return _soft_decode("pl_scan_decode", "scan_decode", _lib.PL_SCAN_EARLY_STOP, plan, llr_logits, num_iter, scale,
+                        early_stop, out_dtype, hard, soft, ext, iters)
 
 
 def pack_bits(bits):
