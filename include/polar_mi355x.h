@@ -49,6 +49,8 @@
  *   pl_llr_quantize / pl_scq_decode: no reference counterpart (fixed-point SC on int8 LLRs; the contract
  *                    is stated below)
  *   pl_ae_decode     no reference counterpart (automorphism-ensemble SC; the contract is stated below)
+ *   pl_pac_encode / pl_pac_decode: no reference counterpart (PAC codes: convolutional precoder and list
+ *                    decoder; the contract is stated below)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -550,6 +552,44 @@ int pl_scq_decode(const pl_plan* plan, const int8_t* llr_q, int64_t bs, int32_t 
  * stream of another device.  Every check but the last runs before any HIP call.  NaN inputs are not supported. */
 int pl_ae_decode(const pl_plan* plan, const float* llr_logits, int64_t bs, const uint16_t* perms, int32_t num_perms,
                  void* out_bits, int32_t out_kind, int32_t* best_idx, float* best_metric, void* hip_stream);
+
+/* PAC codes (polarization-adjusted convolutional codes, Arikan 2019; polar_amd.PACEncoder, polar_amd.PAC_Dec;
+ * csrc/pac_kernel.hip; restated in numpy by tests/golden/pac_ref.py, which the kernels equal value for value).
+ * The reference has no PAC code.  A rate-1 convolutional precoder sits in front of the polar transform; the
+ * frozen set is the rate profile (for the Reed-Muller profile: the row-weight sets of the reference).
+ * Code.  plan: its n (a power of two, 2 <= n <= 1024) and frozen set (k information positions, ascending) are
+ * used.  conv_mask: the generator (c_0, ..., c_m), bit j = c_j, c_0 = 1, 0 <= m <= 31.  The data word v has n
+ * entries: the k data bits at the information positions, 0 elsewhere.  u_i = XOR_{j = 0..m} c_j v_{i-j}, v at a
+ * negative index = 0; equivalently, with a 32-bit register r holding v_i at bit 0, v_{i-1} at bit 1, ...,
+ * u_i = parity(r & conv_mask).  The codeword is x = u G_n, the transform and bit order of the plain encoder.
+ * conv_mask = 1 is the plain polar code.
+ * pl_pac_encode: data_bits [bs, k] fp32 (nonzero = 1) -> codewords [bs, n] fp32 0/1.
+ * pl_pac_decode: a list decoder with the min-sum f, every value fp32.  llr_logits [bs, n] fp32 logits
+ * log P(1)/P(0), negated inside: a positive LLR favours 0.  lmax = the plan's llr_max.
+ *     f(x, y) = sign(x) sign(y) min(|x|, |y|, lmax);   g(x, y, b) = (b ? -x : x) + y, one fp32 add, not clipped.
+ * Partial sums are built from u, not v.  Leaf i with LLR l, for each path: u0 = parity((r << 1) & conv_mask), the
+ * precoder's output for v_i = 0; choosing v gives u = u0 ^ v; the path metric grows by |l| when u != (l < 0), by
+ * 0 otherwise; r becomes (r << 1) | v.  A frozen leaf takes v = 0 -- its u is u0, which need not be 0.  An
+ * information leaf makes 2L candidates, candidate c < L = (path c, v = 0), c >= L = (path c - L, v = 1); the L
+ * smallest metrics survive, ordered by (metric, candidate index).  Path 0 starts at metric 0, the others at
+ * +inf (inf + x = inf: the same order rule covers them).
+ *   out_bits [bs, k], PL_OUT_F32 / PL_OUT_U8: the v bits of the lowest-metric path (the first minimum) at the
+ *     information positions;
+ *   out_pm [bs, list_size] fp32, may be NULL: the final metrics in ascending (metric, path) order.
+ * list_size: a power of two in 1 ... 32, an argument of the call: the plan's own list_size is not used, the plan
+ * supplies n, the frozen set and llr_max.  Every operation is an fp32 add, min, negate or compare.
+ * No workspace, no allocation, no host synchronisation: one launch on the caller's stream, capturable into a
+ * HIP graph.  Natural alignment only.  bs == 0 is PL_OK with no launch.
+ * PL_EINVAL (the message names the argument): a NULL plan, conv_mask with bit 0 clear, list_size not a power of two
+ * in 1 ... 32, bs negative, an unknown out_kind, a NULL data_bits / codewords / llr_logits / out_bits with bs > 0,
+ * a stream of another device.  PL_ENOTSUP: a PL_F_EXACT plan, a plan with a CRC set, and an (n, list_size) whose
+ * state, 4 (L n + n + 2 L max(n/32, 1) + 2 L) + L log2 n bytes, does not fit one work-group's LDS share of
+ * 160 KiB: n <= 1024 (n = 1024 with list_size 32 fits); pl_pac_encode has the same bound on n.  NaN inputs are
+ * not supported. */
+int pl_pac_encode(const pl_plan* plan, uint32_t conv_mask, const float* data_bits, int64_t bs, float* codewords,
+                  void* hip_stream);
+int pl_pac_decode(const pl_plan* plan, uint32_t conv_mask, int32_t list_size, const float* llr_logits, int64_t bs,
+                  void* out_bits, int32_t out_kind, float* out_pm, void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

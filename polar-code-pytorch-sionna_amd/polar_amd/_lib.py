@@ -81,6 +81,8 @@ def _declare(L):
     L.pl_genie_count.argtypes = [i32, i32, ctypes.c_float, P, P, i64, P, P, P]
     L.pl_bp_decode.argtypes = [P, P, i64, i32, ctypes.c_float, u32, P, i32, P, P, P, P]
     L.pl_scan_decode.argtypes = [P, P, i64, i32, ctypes.c_float, u32, P, i32, P, P, P, P]
+    L.pl_pac_encode.argtypes = [P, u32, P, i64, P, P]
+    L.pl_pac_decode.argtypes = [P, u32, i32, P, i64, P, i32, P, P]
     L.pl_scf_workspace_size.argtypes = [P, i64, i32]
     L.pl_scf_workspace_size.restype = ctypes.c_size_t
     L.pl_scf_decode.argtypes = [P, P, i64, i32, P, i32, P, P, P, P, ctypes.c_size_t, P]
@@ -97,7 +99,8 @@ def _declare(L):
               L.pl_hybrid_decode, L.pl_crc_status, L.pl_nr_awgn_qpsk_llr, L.pl_count_errors_packed,
               L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr, L.pl_osd_plan_create, L.pl_osd_plan_destroy,
               L.pl_osd_plan_info, L.pl_osd_decode, L.pl_genie_count, L.pl_bp_decode, L.pl_scf_decode,
-              L.pl_llr_quantize, L.pl_scq_decode, L.pl_ae_decode, L.pl_scan_decode):
+              L.pl_llr_quantize, L.pl_scq_decode, L.pl_ae_decode, L.pl_scan_decode, L.pl_pac_encode,
+              L.pl_pac_decode):
         f.restype = ctypes.c_int
     return L
 
@@ -139,6 +142,7 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_osd_plan_create", "pl_osd_plan_destroy", "pl_osd_plan_info", "pl_osd_decode",
                     "pl_genie_count", "pl_bp_decode", "pl_scf_workspace_size", "pl_scf_decode",
                     "pl_llr_quantize", "pl_scq_decode", "pl_ae_decode", "pl_scan_decode",
+                    "pl_pac_encode", "pl_pac_decode",
                     "pl_last_error_string", "pl_version")
 
 

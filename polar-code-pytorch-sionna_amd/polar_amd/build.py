@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libpolar_mi355x.so")
 KCACHE = os.path.join(HERE, "kcache")
 SOURCES = ["sc_kernel.hip", "scl_kernel.hip", "encode_kernel.hip", "ratematch_kernel.hip", "channel_kernel.hip",
            "clock_kernel.hip", "hybrid_kernel.hip", "osd_kernel.hip", "genie_kernel.hip", "bp_kernel.hip",
-           "scf_kernel.hip", "scq_kernel.hip", "ae_kernel.hip", "scan_kernel.hip", "capi.cpp", "jit.cpp"]
+           "scf_kernel.hip", "scq_kernel.hip", "ae_kernel.hip", "scan_kernel.hip", "pac_kernel.hip", "capi.cpp", "jit.cpp"]
 # scl_tree_kernel.hip is compiled once per list size (its instantiations, in parallel) and once
 # for the launcher: (object name, source, defines)
 UNITS = [(s + ".o", s, []) for s in SOURCES] + \

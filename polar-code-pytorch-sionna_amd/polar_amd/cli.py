@@ -23,6 +23,11 @@ BER counts codeword bits.
 (exact or minsum, the latter scaled by --bp_scale), --bp_early_stop ends a row once its decisions re-encode.
 'scan' in --algos adds the soft-cancellation decoder (SCAN_Dec, pl_scan_decode): --scan_iter iterations (default 2)
 of --scan_f (exact or minsum); --code plain, n <= 2048.
+'pac' in --algos adds the PAC code on the same rate profile (PACEncoder + PAC_Dec, pl_pac_encode / pl_pac_decode):
+the convolutional precoder --pac_conv (octal, default 133) in front of the polar transform, list-decoded with
+--pac_list paths (default 32); --code plain, n <= 1024; the leg runs the op-by-op model (System_AWGN_model), as its
+codewords are not the plain code's.  With 'osd' also in --algos a second OSD leg, "OSD-t of the PAC code", decodes
+the PAC code's own generator matrix: the maximum-likelihood yardstick of that code.
 'scf' in --algos adds the CRC-aided SC-Flip decoder (SCF_Dec, pl_scf_decode) with --scf_flips candidate
 positions a row and the f of --scf_f; it needs --code 5g, the only code here with a CRC.
 'ae' in --algos adds the automorphism-ensemble SC decoder (AE_Dec, pl_ae_decode): --ae_perms permuted SC
@@ -88,6 +93,8 @@ def parse(argv=None):
                     help="BP leg: a row stops once its hard decisions re-encode to those on the code bits")
     ap.add_argument("--scan_iter", type=int, default=2, help="iterations of the SCAN leg ('scan' in --algos)")
     ap.add_argument("--scan_f", choices=["exact", "minsum"], default="exact", help="f of the SCAN leg")
+    ap.add_argument("--pac_list", type=int, default=32, help="list size of the PAC leg ('pac' in --algos): 1, 2, ... 32")
+    ap.add_argument("--pac_conv", default="133", help="PAC leg: the precoder's generator in octal (c_0 first)")
     ap.add_argument("--scf_flips", type=int, default=16,
                     help="SC-Flip leg ('scf' in --algos): candidate positions a row, 0 ... 64")
     ap.add_argument("--scf_f", choices=["exact", "minsum"], default="exact", help="f of the SC-Flip leg")
@@ -142,6 +149,18 @@ def parse(argv=None):
             ap.error(f"'scan' in --algos needs --n <= {SCAN_MAX_N}")
         if c.scan_iter < 1:
             ap.error("--scan_iter must be >= 1")
+    if "pac" in c.algos:
+        from .pac import PAC_MAX_LIST, PAC_MAX_N, conv_from_octal, conv_to_mask
+        if c.code != "plain":
+            ap.error("'pac' in --algos needs --code plain")
+        if c.n > PAC_MAX_N:
+            ap.error(f"'pac' in --algos needs --n <= {PAC_MAX_N}")
+        if not 1 <= c.pac_list <= PAC_MAX_LIST or c.pac_list & (c.pac_list - 1):
+            ap.error(f"--pac_list must be a power of two in [1, {PAC_MAX_LIST}]")
+        try:
+            conv_to_mask(conv_from_octal(c.pac_conv))
+        except ValueError as e:
+            ap.error(f"--pac_conv: {e}")
     if "osd" in c.algos:
         from .osd import check_supported
         if c.code != "plain":
@@ -229,13 +248,19 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
     else:
         enc = channel.DenseEncoder(fp, c.n, G, device=device)
     dev_str = str(device) if device.type == "cuda" else "cpu"
+    if mode in ("pac", "osd_pac"):  # the PAC code on this rate profile: its own encoder, the op-by-op model
+        from .pac import PAC_Dec, PACEncoder, conv_from_octal
+        conv = conv_from_octal(c.pac_conv)
+        enc = PACEncoder(fp, c.n, conv, device=dev_str)
     if mode == "sc":
         dec = SC_Dec(fp, c.n, device=dev_str)
     elif mode == "scl":
         dec = SCL_Dec(fp, c.n, c.list_size, device=dev_str)
-    elif mode == "osd":  # decides codewords: the model compares them with the transmitted ones
+    elif mode in ("osd", "osd_pac"):  # decides codewords: the model compares them with the transmitted ones
         from .osd import OSDecoder
         dec = OSDecoder(c.osd_t, enc, device=dev_str)
+    elif mode == "pac":
+        dec = PAC_Dec(fp, c.n, list_size=c.pac_list, conv=conv, device=dev_str)
     elif mode == "bp":
         from .bp import BP_Dec
         dec = BP_Dec(fp, c.n, num_iter=c.bp_iter, device=dev_str, f=c.bp_f, scale=c.bp_scale,
@@ -254,8 +279,8 @@ def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
         dec = SCQ_Dec(fp, c.n, q_channel=c.scq_qc, q_internal=c.scq_qi, llr_max=c.scq_llr_max, device=dev_str)
     else:
         raise Exception('error...')
-    cw = mode == "osd"
-    if device.type == "cuda" and getattr(c, "llr_producer", "fused") == "fused":
+    cw = mode in ("osd", "osd_pac")
+    if device.type == "cuda" and getattr(c, "llr_producer", "fused") == "fused" and mode not in ("pac", "osd_pac"):
         # one HIP launch for bits/encoder/mapper/channel/demapper; rank r draws stream rows
         # [r*bs, (r+1)*bs) of the seed's stream
         rank = int(os.environ.get("RANK", "0"))
@@ -297,6 +322,10 @@ def main(argv=None):
         codes.append(gen_code(c, f"BP-{c.bp_iter} ({c.bp_f})", "bp", device, gen))
     if "scan" in c.algos:
         codes.append(gen_code(c, f"SCAN-{c.scan_iter} ({c.scan_f})", "scan", device, gen))
+    if "pac" in c.algos:
+        codes.append(gen_code(c, f"PAC-{c.pac_list} (conv {c.pac_conv})", "pac", device, gen))
+        if "osd" in c.algos:
+            codes.append(gen_code(c, f"OSD-{c.osd_t} of the PAC code (codeword BER)", "osd_pac", device, gen))
     if "scf" in c.algos:
         codes.append(gen_code(c, f"SCF-{c.scf_flips} ({c.scf_f})", "scf", device, gen))
     if "ae" in c.algos:

@@ -57,6 +57,13 @@ int launch_bp(const pl_plan* plan, const float* llr, int64_t bs, int num_iter, f
 // soft cancellation (scan_kernel.hip); pl_scan_decode has checked the arguments
 int launch_scan(const pl_plan* plan, const float* llr, int64_t bs, int num_iter, float scale, int early_stop,
                 void* out_bits, int out_kind, float* soft_u, float* ext_x, int32_t* iters, hipStream_t stream);
+// PAC codes (pac_kernel.hip); pl_pac_encode / pl_pac_decode have checked the arguments.  pac_supported: whether
+// the list decoder takes (n, list_size, bs); sets the error string when not
+bool pac_supported(const pl_plan* plan, int list_size, int64_t bs);
+int launch_pac_encode(const pl_plan* plan, uint32_t conv_mask, const float* data, int64_t bs, float* cw,
+                      hipStream_t stream);
+int launch_pac_decode(const pl_plan* plan, uint32_t conv_mask, int list_size, const float* llr, int64_t bs, void* out,
+                      int out_kind, float* out_pm, hipStream_t stream);
 // fixed-point SC on int8 LLRs and the LLR quantiser (scq_kernel.hip); the callers have checked the arguments
 int launch_scq(const pl_plan* plan, const int8_t* llr_q, int64_t bs, int q_internal, void* out, int out_kind,
                hipStream_t stream);

@@ -685,6 +685,74 @@ def scan_decode(plan, llr_logits, num_iter=2, scale=1.0, early_stop=False, out_d
                         early_stop, out_dtype, hard, soft, ext, iters)
 
 
+def _conv_mask(conv_mask):
+    """The uint32 generator mask of a PAC code (bit j = c_j) as a Python int; c_0 must be set."""
+    try:
+        m = conv_mask.__index__()
+    except (AttributeError, TypeError):
+        m = None
+    if m is None or isinstance(conv_mask, bool) or not 0 < m < 2 ** 32 or not m & 1:
+        raise ValueError(f"conv_mask must be an integer in [1, 2^32) with bit 0 (c_0) set, got {conv_mask!r}")
+    return m
+
+
+def pac_encode(plan, conv_mask, data_bits, out=None):
+    """pl_pac_encode: [bs, k] 0/1 data bits -> [bs, n] fp32 codewords of the PAC code (the plan's n <= 1024 and
+    frozen set as rate profile, the generator conv_mask: bit j = c_j): rate-profile scatter, convolutional
+    precoder u_i = XOR_j c_j v_{i-j}, polar transform.  conv_mask = 1 is polar_encode."""
+    _require_cuda(data_bits, "data_bits")
+    m = _conv_mask(conv_mask)
+    u = data_bits
+    if u.dtype != torch.float32 or not u.is_contiguous():
+        u = u.to(torch.float32).contiguous()
+    if u.dim() != 2 or u.shape[1] != plan.k:
+        raise ValueError(f"data_bits must be [bs, {plan.k}], got {tuple(u.shape)}")
+    bs = u.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.n), dtype=torch.float32, device=u.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != (bs, plan.n) \
+            or not out.is_contiguous() or out.device != u.device:
+        raise ValueError("out must be a contiguous float32 [bs, n] tensor on the input's device")
+    with torch.cuda.device(u.device):
+        _lib.check(_lib.lib().pl_pac_encode(plan.handle, m, ctypes.c_void_p(u.data_ptr() if u.numel() else 0), bs,
+                                            ctypes.c_void_p(out.data_ptr() if bs else 0),
+                                            _lib.current_stream_ptr(u.device)), "pl_pac_encode")
+    return out
+
+
+def pac_decode(plan, conv_mask, list_size, llr_logits, out=None, out_dtype=torch.float32, return_pm=False):
+    """pl_pac_decode: list-decode [bs, n] fp32 logits of the PAC code (plan: a min-sum plan without a CRC; its
+    n <= 1024, frozen set and llr_max are used; conv_mask: bit j = c_j) with list_size paths, a power of two in
+    1 ... 32 -> [bs, k] data bits (+ the final path metrics [bs, list_size] fp32, ascending, with return_pm).
+    One launch, no workspace, no host synchronisation: with `out` given and return_pm False the call
+    allocates nothing and can be captured (LaunchGraph)."""
+    _require_cuda(llr_logits, "llr_logits")
+    m = _conv_mask(conv_mask)
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != plan.n:
+        raise ValueError(f"llr_logits must be [bs, {plan.n}], got {tuple(x.shape)}")
+    list_size = int(list_size)
+    if not 1 <= list_size <= 32 or list_size & (list_size - 1):
+        raise ValueError(f"list_size must be a power of two in [1, 32], got {list_size}")
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.k), dtype=out_dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.shape != (bs, plan.k) or not out.is_contiguous() \
+            or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+    pm = torch.empty((bs, list_size), dtype=torch.float32, device=x.device) if return_pm else None
+
+    def ptr(v):
+        return ctypes.c_void_p(v.data_ptr() if v is not None and v.numel() > 0 else 0)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_pac_decode(plan.handle, m, list_size, ptr(x), bs, ptr(out), kind, ptr(pm),
+                                            _lib.current_stream_ptr(x.device)), "pl_pac_decode")
+    return (out, pm) if return_pm else out
+
+
 def pack_bits(bits):
     """[..., k] 0/1 tensor -> [rows, ceil(k/32)] int32 words in pl_sc_decode_count's layout."""
     k = bits.shape[-1]
