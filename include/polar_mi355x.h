@@ -51,6 +51,8 @@
  *   pl_ae_decode     no reference counterpart (automorphism-ensemble SC; the contract is stated below)
  *   pl_pac_encode / pl_pac_decode: no reference counterpart (PAC codes: convolutional precoder and list
  *                    decoder; the contract is stated below)
+ *   pl_pcl_table_create / pl_pcl_decode: no reference counterpart (list decoding under parity constraints
+ *                    between the u-bits, "dynamic frozen bits"; the contract is stated below)
  *   pl_plan_kernel / pl_sc_specialize: no reference counterpart (kernel specialisation per
  *                    frozen set, the tree walk of polar_sc.py:54-98 resolved at compile time)
  */
@@ -590,6 +592,62 @@ int pl_pac_encode(const pl_plan* plan, uint32_t conv_mask, const float* data_bit
                   void* hip_stream);
 int pl_pac_decode(const pl_plan* plan, uint32_t conv_mask, int32_t list_size, const float* llr_logits, int64_t bs,
                   void* out_bits, int32_t out_kind, float* out_pm, void* hip_stream);
+
+/* Parity-constrained list decoding (polar_amd.PCL_Dec, polar_amd.dci; csrc/pcl_kernel.hip; restated in numpy by
+ * tests/golden/pcl_ref.py, which the kernel equals value for value).  The reference has no such decoder.  A list
+ * decoder in which a u-bit may be tied to earlier u-bits by an affine parity relation ("dynamic frozen bits"):
+ * distributed CRC bits (38.212 downlink), parity-check polar codes, RM-polar codes with dynamic frozen bits;
+ * pl_pac_decode is the special case of one convolution at every position.
+ * Table.  pl_pcl_table_create(out, plan, C, pos, kind, rhs, mask): HOST arrays, validated on the host against the
+ * plan's n and frozen set, uploaded to the plan's device (the current device must be the plan's).  C >= 0
+ * constraints (the arrays may be NULL when C == 0):
+ *   pos[C]    strictly ascending positions in [0, n), none frozen: a constrained position counts in k and
+ *             appears in the output like any information position;
+ *   kind[C]   PL_PCL_CHECK or PL_PCL_FORCE;
+ *   rhs[C]    0 or 1;
+ *   mask[C][W], W = max(n / 32, 1): bit (j & 31) of word j >> 5 = u-position j takes part; only non-frozen
+ *             positions strictly below pos[c] may be set.
+ * Constraint c states  u[pos[c]] = rhs[c] ^ parity(mask[c] & u).  Any violation is PL_EINVAL with a message that
+ * names the constraint; a table never reaches a launch unvalidated.  pl_pcl_table_info: n, k of the plan it was made
+ * for and C (any pointer may be NULL).  A table is immutable, device-bound and may be used from any stream.
+ * pl_pcl_decode: the list decoder of pl_pac_decode with conv_mask = 1 -- min-sum f clipped at the plan's llr_max,
+ * g one fp32 add, fp32 metrics, llr_logits [bs, n] fp32 log P(1)/P(0) negated inside, every leaf visited, path 0
+ * starting at metric 0 and the others at +inf -- with these leaves:
+ *   frozen leaf        u = 0; the metric grows by |l| when l < 0.
+ *   information leaf   2L candidates, c < L = (path c, u = 0), c >= L = (path c - L, u = 1), each with the
+ *                      parent's metric plus |l| where u != (l < 0); the first L by (metric, candidate index)
+ *                      survive, +inf metrics included.
+ *   FORCE leaf         no fork: path p takes u = rhs ^ parity(mask & u-decisions of p); its metric grows by |l|
+ *                      where u != (l < 0).
+ *   CHECK leaf         the fork and ranking of an information leaf; then every survivor whose own decisions give
+ *                      u_pos ^ parity(mask & decisions) != rhs gets the metric +inf (it is dead, and loses every
+ *                      later ranking against a live candidate).  If no path is alive after a CHECK leaf the row
+ *                      stops at that leaf.
+ * End: the first path of minimum metric is the output.
+ *   out_bits [bs, k], PL_OUT_F32 / PL_OUT_U8: its u-bits at the plan's information positions, ascending,
+ *     constrained positions included; a row with no path alive is all zero;
+ *   out_pm [bs, list_size] fp32, may be NULL: the final metrics, ascending (metric, path); dead paths are +inf;
+ *   out_ok [bs] bytes, may be NULL: 1 = a live path (finite metric) was output;
+ *   out_stop [bs] int32, may be NULL: the leaf index at which the row stopped, n if it ran to the end.
+ * list_size: a power of two in 1 ... 32, an argument of the call (the plan's own is not used).  No workspace, no
+ * allocation, no host synchronisation: one launch on the caller's stream, capturable into a HIP graph.  Natural
+ * alignment only.  bs == 0 is PL_OK with no launch.
+ * PL_EINVAL (the message names the argument): a NULL plan or table, a table made for another n or frozen set or
+ * on another device, list_size not a power of two in 1 ... 32, bs negative, an unknown out_kind, a NULL llr_logits
+ * / out_bits with bs > 0, a stream of another device.  PL_ENOTSUP: a PL_F_EXACT plan, a plan with a CRC set, and an
+ * (n, list_size) whose state, 4 (L n + n + 2 L max(n/32, 1) + 2 L) + L log2 n bytes, does not fit one
+ * work-group's LDS share of 160 KiB: n <= 1024 (n = 1024 with list_size 32 fits); pl_pcl_table_create has the
+ * same bound on n.  NaN inputs are not supported. */
+#define PL_PCL_CHECK 0
+#define PL_PCL_FORCE 1
+typedef struct pl_pcl_table pl_pcl_table;
+int pl_pcl_table_create(pl_pcl_table** out, const pl_plan* plan, int32_t num_constraints, const int32_t* pos,
+                        const uint8_t* kind, const uint8_t* rhs, const uint32_t* mask);
+int pl_pcl_table_destroy(pl_pcl_table* table);
+int pl_pcl_table_info(const pl_pcl_table* table, int32_t* n, int32_t* k, int32_t* num_constraints);
+int pl_pcl_decode(const pl_plan* plan, const pl_pcl_table* table, int32_t list_size, const float* llr_logits,
+                  int64_t bs, void* out_bits, int32_t out_kind, float* out_pm, uint8_t* out_ok, int32_t* out_stop,
+                  void* hip_stream);
 
 /* pl_clock_probe: diagnostics, not on the reference's path.  One wave runs iters dependent VALU adds
  * and writes ticks[0] = s_memtime cycles (shader clock), ticks[1] = s_memrealtime ticks (100 MHz)

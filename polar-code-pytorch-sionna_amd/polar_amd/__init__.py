@@ -14,11 +14,13 @@ from .design import bit_channel_errors, select_frozen, design_frozen_pos  # noqa
 from .bp import BP_Dec  # noqa: F401
 from .scan import SCAN_Dec  # noqa: F401
 from .pac import PACEncoder, PAC_Dec, conv_from_octal  # noqa: F401
+from .pcl import PCL_Dec, pack_constraints  # noqa: F401
+from .dci import DCIEncoder, DCIDecoder  # noqa: F401
 from .scf import SCF_Dec  # noqa: F401
 from .ae import AE_Dec  # noqa: F401
 from . import automorphism  # noqa: F401
 from .quant import SCQ_Dec  # noqa: F401
 
-__all__ = ["SC_Dec", "SCL_Dec", "BP_Dec", "SCAN_Dec", "PACEncoder", "PAC_Dec", "conv_from_octal", "SCF_Dec", "AE_Dec", "automorphism", "SCQ_Dec", "F2", "get_Kern_frozen_bits", "reference_frozen_pos", "frozen_mask", "ops",
+__all__ = ["SC_Dec", "SCL_Dec", "BP_Dec", "SCAN_Dec", "PACEncoder", "PAC_Dec", "conv_from_octal", "PCL_Dec", "pack_constraints", "DCIEncoder", "DCIDecoder", "SCF_Dec", "AE_Dec", "automorphism", "SCQ_Dec", "F2", "get_Kern_frozen_bits", "reference_frozen_pos", "frozen_mask", "ops",
            "CRCEncoder", "CRCDecoder", "int_mod_2", "OSDecoder", "bit_channel_errors", "select_frozen",
            "design_frozen_pos"]

@@ -22,6 +22,7 @@ PL_PLAN_GENERIC, PL_PLAN_CACHE_ONLY, PL_PLAN_FAST_SCL, PL_PLAN_JIT = 1, 2, 4, 8
 PL_KERNEL_GENERIC, PL_KERNEL_SPECIALIZED, PL_KERNEL_SCL_SUBTREE = 0, 1, 2
 PL_BP_EARLY_STOP = 1
 PL_SCAN_EARLY_STOP = 1
+PL_PCL_CHECK, PL_PCL_FORCE = 0, 1
 
 _lock = threading.Lock()
 _lib = None
@@ -83,6 +84,10 @@ def _declare(L):
     L.pl_scan_decode.argtypes = [P, P, i64, i32, ctypes.c_float, u32, P, i32, P, P, P, P]
     L.pl_pac_encode.argtypes = [P, u32, P, i64, P, P]
     L.pl_pac_decode.argtypes = [P, u32, i32, P, i64, P, i32, P, P]
+    L.pl_pcl_table_create.argtypes = [ctypes.POINTER(P), P, i32, P, P, P, P]
+    L.pl_pcl_table_destroy.argtypes = [P]
+    L.pl_pcl_table_info.argtypes = [P, P, P, P]
+    L.pl_pcl_decode.argtypes = [P, P, i32, P, i64, P, i32, P, P, P, P]
     L.pl_scf_workspace_size.argtypes = [P, i64, i32]
     L.pl_scf_workspace_size.restype = ctypes.c_size_t
     L.pl_scf_decode.argtypes = [P, P, i64, i32, P, i32, P, P, P, P, ctypes.c_size_t, P]
@@ -100,7 +105,7 @@ def _declare(L):
               L.pl_awgn_qam_llr, L.pl_nr_awgn_qam_llr, L.pl_osd_plan_create, L.pl_osd_plan_destroy,
               L.pl_osd_plan_info, L.pl_osd_decode, L.pl_genie_count, L.pl_bp_decode, L.pl_scf_decode,
               L.pl_llr_quantize, L.pl_scq_decode, L.pl_ae_decode, L.pl_scan_decode, L.pl_pac_encode,
-              L.pl_pac_decode):
+              L.pl_pac_decode, L.pl_pcl_table_create, L.pl_pcl_table_destroy, L.pl_pcl_table_info, L.pl_pcl_decode):
         f.restype = ctypes.c_int
     return L
 
@@ -143,6 +148,7 @@ EXPORTED_SYMBOLS = ("pl_plan_create", "pl_plan_destroy", "pl_plan_info", "pl_pla
                     "pl_genie_count", "pl_bp_decode", "pl_scf_workspace_size", "pl_scf_decode",
                     "pl_llr_quantize", "pl_scq_decode", "pl_ae_decode", "pl_scan_decode",
                     "pl_pac_encode", "pl_pac_decode",
+                    "pl_pcl_table_create", "pl_pcl_table_destroy", "pl_pcl_table_info", "pl_pcl_decode",
                     "pl_last_error_string", "pl_version")
 
 
@@ -401,6 +407,50 @@ class OsdPlan:
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib is not None:
             _lib.pl_osd_plan_destroy(h)
+            self._h = None
+
+
+class PclTable:
+    """Owning wrapper of a pl_pcl_table* (the constraints of pl_pcl_decode for the code of `plan`): immutable and
+    device-bound like Plan, made on the plan's device.  pos [C] ascending non-frozen positions, kind [C]
+    PL_PCL_CHECK / PL_PCL_FORCE, rhs [C] 0 / 1, mask [C, max(n / 32, 1)] uint32 packed u-positions below pos; the
+    library validates them (PolarArgumentError names the offending constraint)."""
+
+    def __init__(self, plan, pos, kind, rhs, mask):
+        import numpy as np
+        words = max(plan.n // 32, 1)
+        pos = np.ascontiguousarray(pos, dtype=np.int32).reshape(-1)
+        num = int(pos.shape[0])
+        kind = np.ascontiguousarray(kind, dtype=np.uint8).reshape(-1)
+        rhs = np.ascontiguousarray(rhs, dtype=np.uint8).reshape(-1)
+        mask = np.ascontiguousarray(mask, dtype=np.uint32).reshape(num, -1) if num else np.zeros((0, words), np.uint32)
+        if kind.shape != (num,) or rhs.shape != (num,) or mask.shape != (num, words):
+            raise ValueError(f"{num} constraints need kind [{num}], rhs [{num}] and mask [{num}, {words}], got "
+                             f"{kind.shape}, {rhs.shape}, {mask.shape}")
+        self._h = ctypes.c_void_p()
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if num else ctypes.c_void_p(0)  # noqa: E731
+        with torch.cuda.device(plan.device):
+            check(lib().pl_pcl_table_create(ctypes.byref(self._h), plan.handle, num, ptr(pos), ptr(kind), ptr(rhs),
+                                            ptr(mask)), "pl_pcl_table_create")
+        n_, k_, c_ = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib().pl_pcl_table_info(self._h, ctypes.byref(n_), ctypes.byref(k_), ctypes.byref(c_)), "pl_pcl_table_info")
+        self.n, self.k, self.num_constraints = n_.value, k_.value, c_.value
+        self.device = plan.device
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __deepcopy__(self, memo):  # a copy would double-free the handle
+        raise TypeError("polar_amd PclTable objects are not copyable; build another PclTable")
+
+    def __reduce__(self):
+        raise TypeError("polar_amd PclTable objects are not picklable")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib is not None:
+            _lib.pl_pcl_table_destroy(h)
             self._h = None
 
 

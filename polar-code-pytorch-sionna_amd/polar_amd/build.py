@@ -19,7 +19,8 @@ LIB = os.path.join(HERE, "libpolar_mi355x.so")
 KCACHE = os.path.join(HERE, "kcache")
 SOURCES = ["sc_kernel.hip", "scl_kernel.hip", "encode_kernel.hip", "ratematch_kernel.hip", "channel_kernel.hip",
            "clock_kernel.hip", "hybrid_kernel.hip", "osd_kernel.hip", "genie_kernel.hip", "bp_kernel.hip",
-           "scf_kernel.hip", "scq_kernel.hip", "ae_kernel.hip", "scan_kernel.hip", "pac_kernel.hip", "capi.cpp", "jit.cpp"]
+           "scf_kernel.hip", "scq_kernel.hip", "ae_kernel.hip", "scan_kernel.hip", "pac_kernel.hip", "pcl_kernel.hip",
+           "capi.cpp", "jit.cpp"]
 # scl_tree_kernel.hip is compiled once per list size (its instantiations, in parallel) and once
 # for the launcher: (object name, source, defines)
 UNITS = [(s + ".o", s, []) for s in SOURCES] + \
@@ -125,7 +126,7 @@ def build(force=False, verbose=False, dev=False):
     deps = [os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "butterfly.h"), os.path.join(CSRC, "softplus.h"),
             os.path.join(CSRC, "exactf.h"),
             os.path.join(CSRC, "hybrid.h"), os.path.join(CSRC, "osd.h"), os.path.join(CSRC, "scf.h"), os.path.join(CSRC, "sc_tree.h"),
-            os.path.join(CSRC, "ae.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
+            os.path.join(CSRC, "ae.h"), os.path.join(CSRC, "pcl.h"), os.path.join(HERE, "..", "..", "include", "polar_mi355x.h")]
     jobs = []
     for oname, s, defs in UNITS:
         src = os.path.join(CSRC, s)

@@ -36,6 +36,12 @@ with the f of --ae_f.  It pays on the Reed-Muller sets (k a sum of binomials, e.
 set that admits fewer than --ae_perms such permutations is an argument error.
 'scq' in --algos adds the fixed-point SC decoder (SCQ_Dec, pl_llr_quantize + pl_scq_decode): channel LLRs of
 --scq_qc bits with the largest level at --scq_llr_max, internal LLRs of --scq_qi bits; --code plain only.
+'--code dci simulates the 5G NR downlink chain (polar_amd.dci: DCIEncoder / DCIDecoder with --k, --n as payload and
+code bits, k <= 140, 25 <= n <= 576): CRC24C with the ones prefix and --dci_rnti, the input-bit interleaver (off
+with --dci_tail_crc), downlink rate matching, decoded by the parity-constrained list decoder (pl_pcl_decode) with
+--dci_n_force of the parity bits as FORCE constraints.  The SC leg is list size 1, the scl leg --list_size; a row
+without a surviving path counts as a block error.  The legs run the op-by-op model (System_AWGN_model): the fused
+producer is uplink-only.
 """
 import argparse
 import math
@@ -74,9 +80,14 @@ def parse(argv=None):
     ap.add_argument("--target_block_errs", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--plot", default=None, help="save the BLER plot here (matplotlib)")
-    ap.add_argument("--code", choices=["plain", "5g"], default="plain",
+    ap.add_argument("--code", choices=["plain", "5g", "dci"], default="plain",
                     help="plain: the (k, n) polar code of main.py; 5g: the 5G NR uplink code with --k, --n as "
-                         "k_target, n_target (CRC, rate matching)")
+                         "k_target, n_target (CRC, rate matching); dci: the 5G NR downlink chain (distributed CRC24C)")
+    ap.add_argument("--dci_rnti", type=lambda v: int(v, 0), default=0, help="--code dci: the 16-bit RNTI (e.g. 0xBEEF)")
+    ap.add_argument("--dci_n_force", type=int, default=0,
+                    help="--code dci: the first parity bits in decoding order that are FORCE constraints, 0 ... 24")
+    ap.add_argument("--dci_tail_crc", action="store_true",
+                    help="--code dci: no input-bit interleaver, all 24 parity bits at the tail")
     ap.add_argument("--hybrid_sc", action="store_true",
                     help="--code 5g, scl leg: SC first, the list decoder only on rows whose CRC fails")
     ap.add_argument("--frozen", choices=["reference", "recompute", "design"], default="reference",
@@ -110,6 +121,20 @@ def parse(argv=None):
                     help="fixed-point SC leg: the logit magnitude of the largest channel level")
     c = ap.parse_args(argv)
     c._error = ap.error
+    if c.code == "dci":
+        extra = [a for a in c.algos if a != "scl"]
+        if extra:
+            ap.error(f"--code dci has an SC and an scl leg only, got {extra} in --algos")
+        if not 1 <= c.k <= 140 or not 25 <= c.n <= 576 or c.k + 24 > c.n:
+            ap.error("--code dci needs 1 <= --k <= 140, 25 <= --n <= 576 and k + 24 <= n")
+        if not 0 <= c.dci_rnti < 1 << 16:
+            ap.error("--dci_rnti must be a 16-bit value")
+        if not 0 <= c.dci_n_force <= 24:
+            ap.error("--dci_n_force must be in [0, 24]")
+        if c.list_size < 1 or c.list_size > 32 or c.list_size & (c.list_size - 1):
+            ap.error("--code dci: --list_size must be a power of two in [1, 32]")
+        if c.llr_device != "cuda":
+            ap.error("--code dci runs on the GPU (--llr_device cuda)")
     if "ae" in c.algos:
         from .ae import AE_MAX_N, AE_MAX_PERMS
         if c.code != "plain":
@@ -226,11 +251,26 @@ def gen_code_5g(c, name, mode, device, generator=None):
     return [model, name]
 
 
+def gen_code_dci(c, name, mode, device, generator=None):
+    """[model, name] of the 5G NR downlink chain (payload, code bits) = (--k, --n) on a GPU, op by op."""
+    from . import channel
+    from .dci import DCIDecoder, DCIEncoder
+    if device.type != "cuda":
+        raise ValueError("--code dci runs on the GPU (--llr_device cuda)")
+    enc = DCIEncoder(c.k, c.n, rnti=c.dci_rnti, interleave=not c.dci_tail_crc, device=str(device))
+    dec = DCIDecoder(enc, list_size=1 if mode == "sc" else c.list_size, n_force=c.dci_n_force)
+    model = channel.System_AWGN_model(c.n, c.k, enc, dec, device=device, generator=generator,
+                                      num_bits_per_symbol=getattr(c, "num_bits_per_symbol", 2))
+    return [model, name]
+
+
 def gen_code(c, name, mode, device, generator=None):  # main.py:32-41
     from . import channel, frozen
     from .decoders import SC_Dec, SCL_Dec
     if getattr(c, "code", "plain") == "5g":
         return gen_code_5g(c, name, mode, device, generator)
+    if getattr(c, "code", "plain") == "dci":
+        return gen_code_dci(c, name, mode, device, generator)
     assert math.log(c.n, 2).is_integer()
     G, _, fp = frozen.get_Kern_frozen_bits(c.n, c.n - c.k, frozen.F2)
     if c.frozen == "reference":

@@ -753,6 +753,53 @@ def pac_decode(plan, conv_mask, list_size, llr_logits, out=None, out_dtype=torch
     return (out, pm) if return_pm else out
 
 
+def pcl_decode(plan, table, list_size, llr_logits, out=None, out_dtype=torch.float32, return_pm=False,
+               return_status=False, pm=None, ok=None, stop=None):
+    """pl_pcl_decode: list-decode [bs, n] fp32 logits under the parity constraints of `table` (_lib.PclTable, made
+    for `plan`: a min-sum plan without a CRC; its n <= 1024, frozen set and llr_max are used) with list_size paths, a
+    power of two in 1 ... 32 -> [bs, k] u-bits at the information positions, constrained positions included, all
+    zero for a row with no path left.  return_pm adds the final metrics [bs, list_size] fp32, ascending, +inf for
+    dead paths; return_status adds ok [bs] uint8 (1 = a live path was output) and stop [bs] int32 (the leaf at which
+    the row stopped, n if it ran to the end).  The returned tuple is (bits[, pm][, ok, stop]).  pm / ok / stop may be
+    given as preallocated tensors.  One launch, no workspace, no host synchronisation: with every requested output
+    given the call allocates nothing and can be captured (LaunchGraph)."""
+    _require_cuda(llr_logits, "llr_logits")
+    x = llr_logits
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != plan.n:
+        raise ValueError(f"llr_logits must be [bs, {plan.n}], got {tuple(x.shape)}")
+    list_size = int(list_size)
+    if not 1 <= list_size <= 32 or list_size & (list_size - 1):
+        raise ValueError(f"list_size must be a power of two in [1, 32], got {list_size}")
+    bs = x.shape[0]
+    if out is None:
+        out = torch.empty((bs, plan.k), dtype=out_dtype, device=x.device)
+    elif not isinstance(out, torch.Tensor) or out.shape != (bs, plan.k) or not out.is_contiguous() \
+            or out.device != x.device:
+        raise ValueError("out must be a contiguous [bs, k] tensor on the input's device")
+    kind = _out_kind(out.dtype)
+
+    def side(t, want, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=x.device) if want else None
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.shape != shape or not t.is_contiguous() \
+                or t.device != x.device:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the input's device")
+        return t
+    pm = side(pm, return_pm, (bs, list_size), torch.float32, "pm")
+    ok = side(ok, return_status, (bs,), torch.uint8, "ok")
+    stop = side(stop, return_status, (bs,), torch.int32, "stop")
+
+    def ptr(v):
+        return ctypes.c_void_p(v.data_ptr() if v is not None and v.numel() > 0 else 0)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().pl_pcl_decode(plan.handle, table.handle, list_size, ptr(x), bs, ptr(out), kind, ptr(pm),
+                                            ptr(ok), ptr(stop), _lib.current_stream_ptr(x.device)), "pl_pcl_decode")
+    res = (out,) + ((pm,) if return_pm else ()) + ((ok, stop) if return_status else ())
+    return res if len(res) > 1 else out
+
+
 def pack_bits(bits):
     """[..., k] 0/1 tensor -> [rows, ceil(k/32)] int32 words in pl_sc_decode_count's layout."""
     k = bits.shape[-1]
